@@ -16,11 +16,18 @@ HBM.  --config picks the BASELINE.json workload:
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --gpus N ...        (no launcher: bench.py starts its own N ranks, see self_launch())
 
-Rank 0 prints ONE JSON line: whole-job Msamples/s, the HBM roofline of the dominant
-kernel (HIP-event timed inside the timed region) and, at N=1, the reference's scipy
-CPU path timed on this box's host cores on a bounded sample.  At N > 1 the timed step includes the
-all-gather of the --tile spectrogram tile; after the timed region the same K steps are repeated without
-any gather and with each of the three tile sizes (`legs`: compute_ms / gather_ms separately).
+Rank 0 prints ONE JSON line: whole-job Msamples/s (`value`) and `ms_per_step`, the mean wall clock of the K timed
+steps.  At N > 1 the timed step includes the all-gather of the --tile spectrogram tile.  A plain run does nothing
+else: it sets up, warms up, times the K steps, writes their outputs if --dump-outputs is given and prints the line.
+
+With --full the line also carries everything else the benchmark measures or checks: the HBM roofline of the dominant
+kernel (HIP events around every launch inside the timed region), the device-copy ceiling and the engine clock, the
+parity subset against the CPU oracle (`invalid` if it fails), at N=1 the reference's scipy CPU path timed on the
+host's cores on a bounded sample, the hipGraph and facade legs, and at N > 1 the same K steps repeated without any
+gather and with each of the three tile sizes (`legs`: compute_ms / gather_ms separately).
+
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR     (DIR/{filtered,spectrogram,envelope}.npy)
 """
 
 import argparse
@@ -124,7 +131,18 @@ def parse():
                     help='N=1: skip the leg (outside the timed region) that runs the same slab through the drop-in '
                          'surface -- ArrayLoader -> BufferedFilter.update() -> recompute_all() -- and reports '
                          'facade_ms_per_step next to ms_per_step')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline figure: HIP events around every launch in the timed region '
+                         '(kernels, roofline), the device-copy ceiling, the engine clock, the parity subset against '
+                         'the oracle, the CPU baseline, the hipGraph and facade legs at N = 1 and the compute / tile '
+                         'legs at N > 1.  Without it a run sets up, warms up, times the K steps and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's filtered trace, "
+                         'spectrogram and envelope) as DIR/<name>.npy, float32, at most 64 MB in all: whole arrays '
+                         'if they fit, otherwise the same seeded windows in every run with the same arguments')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     cfg = CONFIGS[args.config]
     for key in ('channels', 'seconds', 'rate', 'nfft', 'hop', 'order', 'env'):
         if getattr(args, key) is None:
@@ -336,6 +354,42 @@ def parity_subset(args, hipdsp, ctx, dx, df, ds, de, T, nd, sos, esos, extra=())
     return float(worst)
 
 
+DUMP_BYTES = 60_000_000      # the .npy files of --dump-outputs together, headers included, stay under 64 MB
+DUMP_WINDOW = 1 << 16        # floats per sampled window: 64 K samples of a trace, 63 frames of a 2048-point PSD
+
+
+def dump_windows(shape, share, seed):
+    """What --dump-outputs writes of a (channels, rows, *row_shape) float32 array within `share` bytes: (None, rows)
+    for the whole array if it fits, else (picks, rows) -- sorted (channel, first row) of windows of `rows` consecutive
+    rows, drawn by a generator seeded with `seed` alone, so that the same shape gives the same windows in every run."""
+    C, L = shape[:2]
+    row = int(np.prod(shape[2:], dtype=np.int64))
+    if 4*C*L*row <= share:
+        return None, L
+    rows = max(1, min(L, DUMP_WINDOW//row))
+    n = share//(4*rows*row)
+    rng = np.random.default_rng(seed)
+    return sorted(zip(rng.integers(0, C, n).tolist(), rng.integers(0, L - rows + 1, n).tolist())), rows
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every float32 DeviceArray of `arrays` (name -> array) as path/<name>.npy, whole or as the windows
+    dump_windows picks within an equal share of DUMP_BYTES, stacked to (windows, rows, *row_shape)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES//len(arrays)
+    for k, (name, a) in enumerate(arrays.items()):
+        picks, rows = dump_windows(a.shape, share, 1234 + k)
+        if picks is None:
+            out = a.to_host()
+        else:
+            L, tail = a.shape[1], a.shape[2:]
+            row = int(np.prod(tail, dtype=np.int64))
+            out = np.empty((len(picks), rows) + tail, dtype=np.float32)
+            for i, (c, r0) in enumerate(picks):
+                out[i] = a.view((c*L + r0)*row, (rows,) + tail).to_host()
+        np.save(os.path.join(path, name + '.npy'), out)
+
+
 class TorchGather:
     """All-gather of the spectrogram tile with torch.distributed (RCCL at backend 'nccl').  The tile is copied out
     of the rank's spectrogram ON THE COMPUTE STREAM right behind the forward sweep (0.03 ms for the visible tile) into
@@ -495,7 +549,9 @@ def tile_leg_record(name, seconds_of_recording, gb, world, steps, gdt, compute_d
             'step_ms': round(gdt/steps*1e3, 4),                          # compute + gather, overlapped
             'gather_ms': round(alone_s*1e3, 4),                          # the gather alone on the device
             'gather_exposed_ms': round((gdt - compute_dt)/steps*1e3, 4),
-            'gather_GBps_per_rank_in': round(gb*(world - 1)/alone_s, 1) if world > 1 and alone_s > 0 else None}
+            # (three significant figures: a gather over gloo on a busy host runs at well under 0.1 GB/s, which a fixed
+            # decimal would report as 0.0)
+            'gather_GBps_per_rank_in': float(f'{gb*(world - 1)/alone_s:.3g}') if world > 1 and alone_s > 0 else None}
 
 
 def rehearse_legs(args):
@@ -709,20 +765,21 @@ def main():
 
     # measured device-copy ceiling (read + write of one trace), reported next to the 8 TB/s spec peak as SURVEY 8d
     # asks; untimed, before the steps: the float4-per-thread copy that reaches the part's streaming ceiling
-    # (hipdsp_copy_probe) and, for comparison with earlier rounds' lines, hipMemcpy D2D
-    ca, cb, cc = ctx.event(), ctx.event(), ctx.event()
-    nbytes = 4*C*T//16*16
-    hipdsp.check(hipdsp.lib.hipdsp_copy_probe(ctx.handle, hipdsp._p(de), hipdsp._p(dx), nbytes))
-    ctx.record(ca)
-    for _ in range(3):
+    # (hipdsp_copy_probe) and, for comparison with earlier rounds' lines, hipMemcpy D2D (--full)
+    if args.full:
+        ca, cb, cc = ctx.event(), ctx.event(), ctx.event()
+        nbytes = 4*C*T//16*16
         hipdsp.check(hipdsp.lib.hipdsp_copy_probe(ctx.handle, hipdsp._p(de), hipdsp._p(dx), nbytes))
-    ctx.record(cb)
-    for _ in range(3):
-        hipdsp.lib.hipdsp_memcpy_d2d(ctx.handle, hipdsp._p(de), hipdsp._p(dx), 4*C*T)
-    ctx.record(cc)
-    ctx.synchronize()
-    copy_gbps = 3*2.0*nbytes/(ctx.elapsed_ms(ca, cb)*1e-3)/1e9
-    memcpy_gbps = 3*8.0*C*T/(ctx.elapsed_ms(cb, cc)*1e-3)/1e9
+        ctx.record(ca)
+        for _ in range(3):
+            hipdsp.check(hipdsp.lib.hipdsp_copy_probe(ctx.handle, hipdsp._p(de), hipdsp._p(dx), nbytes))
+        ctx.record(cb)
+        for _ in range(3):
+            hipdsp.lib.hipdsp_memcpy_d2d(ctx.handle, hipdsp._p(de), hipdsp._p(dx), 4*C*T)
+        ctx.record(cc)
+        ctx.synchronize()
+        copy_gbps = 3*2.0*nbytes/(ctx.elapsed_ms(ca, cb)*1e-3)/1e9
+        memcpy_gbps = 3*8.0*C*T/(ctx.elapsed_ms(cb, cc)*1e-3)/1e9
 
     # The fused forward sweep (band-pass + envelope states + spectrogram in one launch) whenever the library
     # covers the shape: one untimed trial decides.
@@ -764,8 +821,9 @@ def main():
         return TorchGather(torch, dist, hipdsp, ctx, tspec, tf, world, args.backend, cstream)
 
     n_ev = 7
-    events = [[ctx.event() for _ in range(n_ev)] for _ in range(args.steps)]
-    mids = [ctx.event() for _ in range(args.steps)]
+    # (HIP events around every launch of the timed steps: --full only, a plain run times the steps alone)
+    events = [[ctx.event() for _ in range(n_ev)] for _ in range(args.steps)] if args.full else None
+    mids = [ctx.event() for _ in range(args.steps)] if args.full else None
     fused = not args.no_fuse
 
     def step(i, gatherer):
@@ -855,7 +913,50 @@ def main():
         return dt
 
     main_gather = make_gatherer(args.tile) if multi else None
-    dt = timed_run(main_gather)
+    dt = timed_run(main_gather, record=args.full)
+    if args.dump_outputs and rank == 0:
+        # what the last timed step left for its caller, before anything below launches on these buffers again
+        dump_outputs(args.dump_outputs, {'filtered': df, 'spectrogram': ds, 'envelope': de})
+
+    samples = float(C)*T*world
+    line = {
+        'metric': 'Msamples/s spectrogram+bandpass, 64ch x 96kHz',
+        'value': samples/(dt/args.steps)/1e6,
+        'unit': 'Msamples/s',
+        'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
+        'ms_per_step': dt/args.steps*1e3,
+        'higher_is_better': True,
+        'scaling': args.scaling,
+        'vs_baseline': None,
+        'dtype': 'f32 I/O, f64 IIR state',
+        'data': 'synthetic',
+        'config': {
+            'workload': (f'{args.config_name}, STRONG scaling: {total_channels} channels in total = ' if total_channels
+                         else f'{args.config_name}: synthetic ') + f'{C} ch/GPU x {args.seconds:g} s x '
+                        f'{args.rate/1000:g} kHz float32; bandpass {args.hp:g}-{args.lp:g} Hz '
+                        f'order {args.order} -> spectrogram nfft {args.nfft} hop {args.hop} '
+                        f'+ envelope {args.env:g} Hz',
+            'channels_per_gpu': C, 'frames': T, 'spectrogram_frames': nd,
+            'parallelism': f'channel shard x{world}' +
+                           (f', all-gather ({args.gather}) of the {args.tile} spectrogram tile '
+                            f'({4*C*tile_frames_of(args.tile)*F/1e9:.2f} GB per rank) copied out behind the forward sweep, gathered behind the backward sweep (under the next forward sweep), '
+                            f'{reserve} CUs left to RCCL' if multi else ''),
+            'iir_warmup_samples': {'bandpass': warm_f, 'envelope': warm_e},
+            'streams': ('spectrogram on a second stream next to the envelope backward sweep '
+                        '(their event-bracketed times overlap)' if overlap else 'one compute stream'),
+            'envelope_forward': ('state checkpoints, ' + ('fused into the band-pass kernel' if fused else 'own launch')),
+            'envelope_buffer': (f'best of {args.write_probe} allocations by memset time (hipdsp_malloc_probed)'
+                                if args.write_probe > 1 else 'plain allocation'),
+            'spectrogram': ('FFT waves inside the forward sweep (filtered tiles from LDS)' if fuse3 else 'own launch'),
+        },
+    }
+    if not args.full:
+        if rank == 0:
+            sys.stdout.flush()
+            os.write(result_fd, (json.dumps(line) + '\n').encode())
+        if multi:
+            dist.destroy_process_group()
+        return
 
     # per-kernel averages from the HIP events recorded inside the timed region
     if fuse3:
@@ -1036,37 +1137,7 @@ def main():
             facade = {'failed': f'{type(err).__name__}: {err}'[:300]}
 
     if rank == 0:
-        samples = float(C)*T*world
-        line = {
-            'metric': 'Msamples/s spectrogram+bandpass, 64ch x 96kHz',
-            'value': samples/(dt/args.steps)/1e6,
-            'unit': 'Msamples/s',
-            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
-            'ms_per_step': dt/args.steps*1e3,
-            'higher_is_better': True,
-            'scaling': args.scaling,
-            'vs_baseline': None,
-            'dtype': 'f32 I/O, f64 IIR state',
-            'data': 'synthetic',
-            'config': {
-                'workload': (f'{args.config_name}, STRONG scaling: {total_channels} channels in total = ' if total_channels
-                             else f'{args.config_name}: synthetic ') + f'{C} ch/GPU x {args.seconds:g} s x '
-                            f'{args.rate/1000:g} kHz float32; bandpass {args.hp:g}-{args.lp:g} Hz '
-                            f'order {args.order} -> spectrogram nfft {args.nfft} hop {args.hop} '
-                            f'+ envelope {args.env:g} Hz',
-                'channels_per_gpu': C, 'frames': T, 'spectrogram_frames': nd,
-                'parallelism': f'channel shard x{world}' +
-                               (f', all-gather ({args.gather}) of the {args.tile} spectrogram tile '
-                                f'({4*C*tile_frames_of(args.tile)*F/1e9:.2f} GB per rank) copied out behind the forward sweep, gathered behind the backward sweep (under the next forward sweep), '
-                                f'{reserve} CUs left to RCCL' if multi else ''),
-                'iir_warmup_samples': {'bandpass': warm_f, 'envelope': warm_e},
-                'streams': ('spectrogram on a second stream next to the envelope backward sweep '
-                            '(their event-bracketed times overlap)' if overlap else 'one compute stream'),
-                'envelope_forward': ('state checkpoints, ' + ('fused into the band-pass kernel' if fused else 'own launch')),
-                'envelope_buffer': (f'best of {args.write_probe} allocations by memset time (hipdsp_malloc_probed)'
-                                    if args.write_probe > 1 else 'plain allocation'),
-                'spectrogram': ('FFT waves inside the forward sweep (filtered tiles from LDS)' if fuse3 else 'own launch'),
-            },
+        line.update({
             'roofline': {'bound': 'hbm', 'kernel': dom, 'achieved': round(achieved, 1),
                          'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
                          'frac': round(achieved/HBM_PEAK_GBS, 4), 'traffic': traffic, 'traffic_source': traffic_source,
@@ -1082,7 +1153,7 @@ def main():
             'chain_algorithmic_GBps': round(sum(alg_bytes.values())/(dt/args.steps)/1e9, 1),
             'parity_max_rel_err': parity,
             'cpu_baseline': cpu,
-        }
+        })
         if graph_ms is not None:
             line['graph_ms_per_step'] = graph_ms if isinstance(graph_ms, str) else round(graph_ms, 4)
         if facade is not None:

@@ -6,9 +6,10 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
-from conftest import ROOT
+from conftest import ROOT, rel_err
 
 REQUIRED = ['metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better',
             'scaling', 'vs_baseline', 'dtype', 'data', 'config', 'roofline', 'cpu_baseline']
@@ -23,6 +24,7 @@ def test_flags_and_defaults():
     finally:
         sys.argv = argv
     assert (a.gpus, a.steps, a.warmup) == (1, 10, 3)
+    assert a.full is False and a.dump_outputs is None          # a plain run: the headline figure only
     # BASELINE configs[2]
     assert (a.channels, a.seconds, a.rate, a.nfft, a.hop) == (64, 600.0, 96000.0, 2048, 1024)
     assert (a.hp, a.lp, a.order, a.env) == (300.0, 3000.0, 2, 20.0)
@@ -41,7 +43,7 @@ def test_flags_and_defaults():
         sys.argv = argv
     assert (a1.channels, a1.seconds, a1.rate, a1.nfft, a1.hop, a1.order) == (8, 60.0, 48000.0, 1024, 256, 4)
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--help'], capture_output=True, text=True)
-    for flag in ('--gpus', '--steps', '--warmup'):
+    for flag in ('--gpus', '--steps', '--warmup', '--full', '--dump-outputs'):
         assert flag in out.stdout
 
 
@@ -109,13 +111,22 @@ def test_eight_rank_bookkeeping_of_the_multi_gpu_line():
         assert t['step_ms'] > 0 and t['gather_ms'] > 0
 
 
+
+def test_a_slow_gather_keeps_a_positive_rate():
+    """The legs' gather rate keeps three significant figures: 0.1 GB received per rank in 10 s per gather (gloo on a busy
+    host) is 0.0105 GB/s, not 0.0."""
+    sys.path.insert(0, ROOT)
+    import bench
+    rec = bench.tile_leg_record('visible', 10.0, 0.015, 8, 2, 20.0, 0.0, 10.0)
+    assert rec['gather_GBps_per_rank_in'] == 0.0105 and rec['gather_ms'] == 10000.0
+
 @pytest.mark.gpu
 def test_four_ranks_on_one_gpu_through_the_real_path():
     """... and the real path with as many ranks as a round's GPU box holds next to the test runner (six processes on the
     card at most, this one among them): compute on GPU 0 in every rank, the tile gathers over gloo -- N > 3 for the
     first time through the kernels, the gatherers and the legs."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '4', '--config', '3', '--backend', 'gloo',
-                          '--same-device', '--channels', '4', '--seconds', '20', '--steps', '2', '--warmup', '1'],
+                          '--same-device', '--channels', '4', '--seconds', '20', '--steps', '2', '--warmup', '1', '--full'],
                          capture_output=True, text=True, env=_no_launcher_env(), timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = out.stdout.splitlines()
@@ -134,7 +145,7 @@ def test_four_ranks_on_one_gpu_through_the_real_path():
 @pytest.mark.gpu
 def test_one_json_line_with_the_contract_keys():
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--seconds', '20', '--steps', '2',
-                          '--warmup', '1', '--cpu-sample-seconds', '1'], capture_output=True, text=True, timeout=600)
+                          '--warmup', '1', '--full', '--cpu-sample-seconds', '1'], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = out.stdout.splitlines()
     assert len(lines) == 1, out.stdout[:2000]            # nothing but the JSON line on stdout
@@ -156,7 +167,7 @@ def test_one_json_line_with_the_contract_keys():
 @pytest.mark.gpu
 def test_separate_launches_on_request():
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--seconds', '20', '--steps', '2',
-                          '--warmup', '1', '--no-cpu-baseline', '--no-fuse-spectrogram'], capture_output=True,
+                          '--warmup', '1', '--full', '--no-cpu-baseline', '--no-fuse-spectrogram'], capture_output=True,
                          text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads(out.stdout.splitlines()[-1])
@@ -169,7 +180,7 @@ def test_multi_rank_code_path_prints_only_the_json_line():
     """The N > 1 code path (torch.distributed over RCCL, non-default streams, tile all-gather)
     with a single rank: RCCL's start-up banner must not end up on stdout."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--force-dist', '--seconds', '20',
-                          '--steps', '2', '--warmup', '1', '--no-cpu-baseline'], capture_output=True, text=True,
+                          '--steps', '2', '--warmup', '1', '--full', '--no-cpu-baseline'], capture_output=True, text=True,
                          timeout=600, env=dict(os.environ, MASTER_ADDR='127.0.0.1', MASTER_PORT='29577'))
     assert out.returncode == 0, out.stderr[-2000:]
     lines = out.stdout.splitlines()
@@ -187,13 +198,29 @@ def test_multi_rank_code_path_prints_only_the_json_line():
         assert t['step_ms'] > 0 and t['gather_ms'] >= 0 and t['GB_per_rank'] > 0
 
 
+
+@pytest.mark.gpu
+def test_plain_multi_rank_run_gathers_in_every_step_and_prints_the_headline_only():
+    """The N > 1 code path without --full: the tile all-gather stays inside the timed steps, the legs after them do not
+    run, and the line still comes alone on stdout."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--force-dist', '--seconds', '20',
+                          '--steps', '2', '--warmup', '1'], capture_output=True, text=True, timeout=600,
+                         env=dict(os.environ, MASTER_ADDR='127.0.0.1', MASTER_PORT='29583'))
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = out.stdout.splitlines()
+    assert len(lines) == 1, out.stdout[:2000]
+    d = json.loads(lines[0])
+    assert d['n_gpus'] == 1 and d['steps'] == 2 and d['ms_per_step'] > 0 and 'all-gather' in d['config']['parallelism']
+    for key in ('legs', 'compute_ms', 'gather_ms', 'roofline', 'parity_max_rel_err'):
+        assert key not in d, key
+
 @pytest.mark.gpu
 def test_configs3_rehearsal_through_the_c_abi_gather():
     """BASELINE configs[3]'s shard (32 channels per GPU) with the exchange step taken through the C ABI
     (hipdsp_comm_* / hipdsp_allgather_f32 on a second context) instead of torch.distributed -- one rank here,
     the driver runs the real thing; the fused forward sweep leaves CUs to RCCL's kernel."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--force-dist', '--config', '3', '--seconds',
-                          '60', '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--gather', 'c-abi', '--tile',
+                          '60', '--steps', '2', '--warmup', '1', '--full', '--no-cpu-baseline', '--gather', 'c-abi', '--tile',
                           'window'], capture_output=True, text=True, timeout=600,
                          env=dict(os.environ, MASTER_ADDR='127.0.0.1', MASTER_PORT='29578'))
     assert out.returncode == 0, out.stderr[-2000:]
@@ -211,7 +238,7 @@ def test_configs3_shard_at_full_size():
     the first 2 s of channels {0, 16, 31}, a window at an internal segment border of the fused plan and the last 2 s
     of the last channel with the oracle (filtered trace, envelope, every PSD frame)."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--force-dist', '--config', '3', '--steps',
-                          '2', '--warmup', '1', '--no-cpu-baseline', '--gather', 'c-abi', '--tile', 'window'],
+                          '2', '--warmup', '1', '--full', '--no-cpu-baseline', '--gather', 'c-abi', '--tile', 'window'],
                          capture_output=True, text=True, timeout=900,
                          env=dict(os.environ, MASTER_ADDR='127.0.0.1', MASTER_PORT='29581'))
     assert out.returncode == 0, out.stderr[-2000:]
@@ -234,7 +261,7 @@ def test_gpus_2_without_a_launcher_on_one_gpu():
     launcher around it -- starts two ranks itself; here both on GPU 0 with gloo as the collective backend (a one-GPU
     box), so the whole N > 1 path runs: rendezvous, channel shard, tile gather, max over ranks, ONE line."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--backend', 'gloo',
-                          '--same-device', '--seconds', '20', '--channels', '8', '--steps', '2', '--warmup', '1',
+                          '--same-device', '--seconds', '20', '--channels', '8', '--steps', '2', '--warmup', '1', '--full',
                           '--no-legs'], capture_output=True, text=True, timeout=900, env=_no_launcher_env())
     assert out.returncode == 0, out.stderr[-3000:]
     lines = out.stdout.splitlines()
@@ -248,7 +275,7 @@ def test_gpus_2_without_a_launcher_on_one_gpu():
 @pytest.mark.gpu
 def test_configs1_line():
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--config', '1', '--steps', '3', '--warmup',
-                          '1', '--cpu-sample-seconds', '2'], capture_output=True, text=True, timeout=600)
+                          '1', '--full', '--cpu-sample-seconds', '2'], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads(out.stdout.splitlines()[-1])
     assert 'configs[1]' in d['config']['workload'] and d['config']['channels_per_gpu'] == 4
@@ -274,7 +301,7 @@ def test_facade_leg_runs_the_fused_launch_and_agrees_with_the_direct_path():
     (ArrayLoader -> BufferedFilter.update() -> recompute_all()): it must issue the fused launch, give the direct
     path's numbers bit for bit and cost about the same per step."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--seconds', '30', '--steps', '3', '--warmup',
-                          '1', '--no-cpu-baseline'], capture_output=True, text=True, timeout=600)
+                          '1', '--full', '--no-cpu-baseline'], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads(out.stdout.splitlines()[-1])
     f = d['facade']
@@ -291,10 +318,89 @@ def test_strong_scaling_share_and_graph_leg():
     """--scaling strong: the config's channels in TOTAL over the GPUs (rehearsed here as one rank's share of eight);
     a latency-sized job also reports the step as a replayed hipGraph."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--scaling', 'strong', '--strong-world', '8',
-                          '--seconds', '30', '--steps', '5', '--warmup', '2', '--no-cpu-baseline', '--no-facade'],
+                          '--seconds', '30', '--steps', '5', '--warmup', '2', '--no-cpu-baseline', '--no-facade', '--full'],
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads(out.stdout.splitlines()[-1])
     assert d['scaling'] == 'strong' and d['config']['channels_per_gpu'] == 8 and 'STRONG' in d['config']['workload']
     assert d['parity_max_rel_err'] < 1e-4 and 'invalid' not in d
     assert isinstance(d.get('graph_ms_per_step'), float) and 0 < d['graph_ms_per_step'] < 2*d['ms_per_step']
+
+
+class _HostArray:
+    """What dump_outputs() uses of a DeviceArray (shape, view, to_host), over a host array."""
+
+    def __init__(self, a):
+        self.a, self.shape = a, a.shape
+
+    def view(self, offset, shape):
+        return _HostArray(self.a.reshape(-1)[offset:offset + int(np.prod(shape))].reshape(shape))
+
+    def to_host(self):
+        return self.a.copy()
+
+
+def test_dump_outputs_writes_fixed_windows_under_64_mb(tmp_path):
+    """--dump-outputs: at configs[2]'s size the three outputs are sampled in windows that depend on the shape alone, lie
+    inside the array and stay under 64 MB together; each window holds the rows it names; small arrays go whole."""
+    sys.path.insert(0, ROOT)
+    import bench
+    share = bench.DUMP_BYTES//3
+    total = 0
+    for shape in ((64, 57600000), (64, 56250, 1025)):
+        picks, rows = bench.dump_windows(shape, share, 1234)
+        assert (picks, rows) == bench.dump_windows(shape, share, 1234) and len(picks) > 16 and rows > 32
+        assert all(0 <= c < shape[0] and 0 <= r0 <= shape[1] - rows for c, r0 in picks)
+        total += 4*len(picks)*rows*int(np.prod(shape[2:]))
+    assert bench.dump_windows((4, 1000), share, 1) == (None, 1000)
+    assert total < 2*share
+    arrays = {'filtered': np.arange(2*3000000, dtype=np.float32).reshape(2, 3000000),
+              'spectrogram': np.arange(3*2500*1025, dtype=np.float32).reshape(3, 2500, 1025),
+              'envelope': np.arange(4*1000, dtype=np.float32).reshape(4, 1000)}
+    bench.dump_outputs(str(tmp_path/'out'), {k: _HostArray(v) for k, v in arrays.items()})
+    files = sorted((tmp_path/'out').iterdir())
+    assert [f.name for f in files] == ['envelope.npy', 'filtered.npy', 'spectrogram.npy']
+    assert sum(f.stat().st_size for f in files) < 64e6
+    for k, (name, a) in enumerate(arrays.items()):
+        got = np.load(tmp_path/'out'/(name + '.npy'))
+        assert got.dtype == np.float32
+        picks, rows = bench.dump_windows(a.shape, share, 1234 + k)
+        if picks is None:
+            assert np.array_equal(got, a)
+            continue
+        assert got.shape == (len(picks), rows) + a.shape[2:]
+        for i, (c, r0) in enumerate(picks):
+            assert np.array_equal(got[i], a[c, r0:r0 + rows])
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_outputs(tmp_path):
+    """Without --full the line holds the headline figure and nothing that needs work outside the K timed steps; with
+    --dump-outputs the last step's filtered trace, spectrogram and envelope land as float32 .npy files under 64 MB, on
+    the same windows for the same shape: the fused launch's outputs and the separate launches' agree."""
+    dumps = []
+    for extra in ([], ['--no-fuse-spectrogram']):
+        d = tmp_path/('run%d' % len(dumps))
+        out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--seconds', '20', '--steps', '3',
+                              '--warmup', '1', '--dump-outputs', str(d)] + extra, capture_output=True, text=True,
+                             timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = out.stdout.splitlines()
+        assert len(lines) == 1, out.stdout[:2000]
+        line = json.loads(lines[0])
+        for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+            assert key in line, key
+        assert line['steps'] == 3 and line['unit'] == 'Msamples/s' and line['higher_is_better'] is True
+        assert abs(line['value'] - 64*20*96000/(line['ms_per_step']*1e-3)/1e6) < 1e-6*line['value']
+        for key in ('roofline', 'kernels', 'cpu_baseline', 'parity_max_rel_err', 'facade', 'graph_ms_per_step', 'legs'):
+            assert key not in line, key
+        files = sorted(d.iterdir())
+        assert [f.name for f in files] == ['envelope.npy', 'filtered.npy', 'spectrogram.npy']
+        assert sum(f.stat().st_size for f in files) < 64e6
+        dumps.append({f.name: np.load(f) for f in files})
+        for a in dumps[-1].values():
+            assert a.dtype == np.float32 and a.size > 0 and np.all(np.isfinite(a))
+    for name, a in dumps[0].items():
+        b = dumps[1][name]
+        assert a.shape == b.shape and np.max(np.abs(a)) > 0, name
+        assert rel_err(b, a) < 1e-4, name

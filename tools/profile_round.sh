@@ -9,7 +9,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/prof_$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-CMD="python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline"
+CMD="python3 $R/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats -d $O/trace --output-format csv -- $CMD > $O/trace.log 2>&1
 echo trace done
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/fetch --output-format csv -- $CMD > $O/fetch.log 2>&1
