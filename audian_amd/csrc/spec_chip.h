@@ -67,7 +67,10 @@ __global__ __launch_bounds__(512, 2) void spec_chip_kernel(
     // frame-invariant twiddle bases of this thread (exact fractions of a turn)
     const int k2 = l & 31;                                   // stage 2: W_1024^(k2 t), the same k2 for both butterflies
     const int j3a = l, j3b = res ? 1023 - l : ((l == 0) ? 512 : 1024 - l);      // stage 3 butterflies: a pair of partners
-    auto cis = [](float turn) { return make_float2(__builtin_amdgcn_cosf(turn), -__builtin_amdgcn_sinf(turn)); };   // exp(-2 pi i turn)
+    // exp(-2 pi i turn) to an ulp or so (sincospif): the stage twiddles are powers of these bases up to the 31st, which
+    // multiplies a base's error by up to 31 -- from v_cos_f32 / v_sin_f32 that put the 65536 and 131072 PSDs over the
+    // per-bin bound (tests/test_gpu_spectral_accuracy.py); once per workgroup, outside the frame loop
+    auto cis = [](float turn) { float s, c; sincospif(2.0f * turn, &s, &c); return make_float2(c, -s); };
     float2 w2 = cis((float)k2 * (1.0f / 1024.0f));
     float2 w3a = cis((float)j3a * (1.0f / 32768.0f)), w3b = cis((float)j3b * (1.0f / 32768.0f));
     float2 sa = cis((float)(SB * j3a + res) * (1.0f / (float)NFFT)), sb = cis((float)(SB * j3b + res) * (1.0f / (float)NFFT));   // split twiddles of the first bins

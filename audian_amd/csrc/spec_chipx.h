@@ -56,6 +56,9 @@ __global__ __launch_bounds__(512, 2) void spec_chipx_kernel(
     const int npass = kind == 2 ? 2 : 1;
     const float *seg = xc + frame * (long long)hop;
     auto cis = [](float turn) { return make_float2(__builtin_amdgcn_cosf(turn), -__builtin_amdgcn_sinf(turn)); };   // exp(-2 pi i turn)
+    // the bases of the power chains and of the split twiddles to an ulp or so (sincospif; spec_chip.h's cis): a few calls
+    // per task
+    auto cisx = [](float turn) { float s, c; sincospif(2.0f * turn, &s, &c); return make_float2(c, -s); };
 
     // the pivot of the frame mean: 2048 samples spread over the frame, none of them on its borders
     float pivot;
@@ -74,8 +77,8 @@ __global__ __launch_bounds__(512, 2) void spec_chipx_kernel(
 
     const int k2 = l & 31;                                   // stage 2: W_1024^(k2 t)
     const int j3a = l, j3b = kind == 0 ? ((l == 0) ? 512 : 1024 - l) : 1023 - l;     // stage 3 butterflies: a pair of partners
-    const float2 w2 = cis((float)k2 * (1.0f / 1024.0f));
-    const float2 w3a = cis((float)j3a * (1.0f / 32768.0f)), w3b = cis((float)j3b * (1.0f / 32768.0f));
+    const float2 w2 = cisx((float)k2 * (1.0f / 1024.0f));
+    const float2 w3a = cisx((float)j3a * (1.0f / 32768.0f)), w3b = cisx((float)j3b * (1.0f / 32768.0f));
     const int wr2 = (l >> 5) * (Q + 32) + (l & 31);
     const int ra = pidx(j3a), rb = pidx(j3b);
     const unsigned lo_l = 4u * RX * (unsigned)l, lo_m = 4u * RX * (unsigned)(1023 - l);      // lane offsets of bins RX (l + ..) and their partners
@@ -278,7 +281,7 @@ __global__ __launch_bounds__(512, 2) void spec_chipx_kernel(
         // residue 0: the pairing of spec_chip.h at 65536 -- t' < 16: (ya[t'], yb[31 - t']) k' = l + 1024 t' and (yb[t'], ya[31 - t'])
         // k' = 1024 - l + 1024 t'; thread 0: ya[0] = DC and Nyquist, (ya[t'], ya[32 - t']), (yb[t'], yb[31 - t']), ya[16] = the
         // bin in the middle, which pairs with itself
-        const float2 sa = cis((float)(RX * j3a) * (1.0f / (float)NFFT)), sb = cis((float)(RX * j3b) * (1.0f / (float)NFFT));
+        const float2 sa = cisx((float)(RX * j3a) * (1.0f / (float)NFFT)), sb = cisx((float)(RX * j3b) * (1.0f / (float)NFFT));
         const unsigned loa = 4u * RX * (unsigned)j3a, lma = 4u * RX * (unsigned)(Q - j3a), lob = 4u * RX * (unsigned)j3b,
                        lmb = 4u * RX * (unsigned)(Q - j3b);
         auto put0 = [&](int t, unsigned lo, unsigned lm, float pk, float pm) {
@@ -307,7 +310,7 @@ __global__ __launch_bounds__(512, 2) void spec_chipx_kernel(
         }
     } else if (kind == 1) {
         // residue RX / 2 pairs with itself: k = RX (l + 1024 t) + RX / 2 from (ya[t], yb[31 - t])
-        const float2 sa = cis((float)(RX * l + RX / 2) * (1.0f / (float)NFFT));
+        const float2 sa = cisx((float)(RX * l + RX / 2) * (1.0f / (float)NFFT));
 #pragma unroll
         for (int t = 0; t < R; t++) {
             float pk, pm;
@@ -326,7 +329,7 @@ __global__ __launch_bounds__(512, 2) void spec_chipx_kernel(
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
             for (int t = 0; t < R; t++) asm volatile("" : "+v"(pq[t].x), "+v"(pq[t].y));
-            const float2 s1 = cis((float)(RX * l + r0) * (1.0f / (float)NFFT));
+            const float2 s1 = cisx((float)(RX * l + r0) * (1.0f / (float)NFFT));
 #pragma unroll
             for (int t = 0; t < R; t++) {
                 float pk, pm;
@@ -341,7 +344,7 @@ __global__ __launch_bounds__(512, 2) void spec_chipx_kernel(
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
             for (int t = 0; t < R; t++) asm volatile("" : "+v"(pq[t].x), "+v"(pq[t].y));
-            const float2 s2 = cis((float)(RX * l + RX - r0) * (1.0f / (float)NFFT));
+            const float2 s2 = cisx((float)(RX * l + RX - r0) * (1.0f / (float)NFFT));
 #pragma unroll
             for (int t = 0; t < R; t++) {
                 float pk, pm;

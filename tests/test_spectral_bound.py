@@ -1,0 +1,226 @@
+"""Calibration of the per-bin PSD bound (tests/spectral_bound.py) on the CPU.
+
+A faithful float32 pipeline -- detrend in float64 rounded once, the float64 Hann window rounded to float32, a
+float32 radix-2 FFT with correctly rounded twiddles, the power in float32 -- stays within the bound with at least
+2.5x margin on every signal family and every power of two from 8 to 524288.  Defects a kernel could carry fail it:
+twiddles off by +-1e-6 (about 16 ulp), a window off by +-4e-6, a doubled Nyquist or DC bin, two adjacent bins
+swapped at -60 dB, a detrend by a float32-rounded mean.  The suite's older metric (rel_err < 1e-4 per frame)
+accepts the twiddle defect.  The direct DFT's bound (sqrt(nfft) for sqrt(L)) is calibrated against a sequential
+float32 emulation of spec_direct_kernel.
+"""
+
+import numpy as np
+import pytest
+
+from conftest import rel_err
+import spectral_bound as sb
+
+RATE = 48000.0
+MARGIN = 2.5
+SIZES = [2**k for k in range(3, 20)]
+
+
+def frames_for(nfft):
+    return 4 if nfft <= 8192 else (2 if nfft <= 65536 else 1)
+
+
+def reference(x, nfft, hop, nseg):
+    """float64 PSD (nseg, C, F) of the float32 input (numpy's float64 FFT: the C oracle's numbers to 1e-15)."""
+    from oracle import oracle as orc
+    _, _, S = orc.spectrogram_numpy(x[:(nseg - 1)*hop + nfft].astype(np.float64), RATE, nfft, nfft - hop)
+    return S.transpose(1, 2, 0)
+
+
+def fft32(z, table):
+    """Iterative radix-2 DIT FFT in complex64 along the last axis; `table` holds W_N^k, k < N/2 (complex64)."""
+    N = z.shape[-1]
+    lg = N.bit_length() - 1
+    idx = np.arange(N)
+    rev = np.zeros(N, dtype=np.int64)
+    for b in range(lg):
+        rev |= ((idx >> b) & 1) << (lg - 1 - b)
+    z = z[..., rev].astype(np.complex64)
+    size = 2
+    while size <= N:
+        half = size//2
+        w = table[::N//size][:half]
+        v = z.reshape(z.shape[:-1] + (N//size, size))
+        top = v[..., :half]
+        t = v[..., half:]*w
+        z = np.concatenate([top + t, top - t], axis=-1).reshape(z.shape)
+        size *= 2
+    return z
+
+
+def emulate(x, nfft, hop, nseg, twiddle_err=0.0, window_err=0.0, mean32=False, seed=0):
+    """A float32 spectrogram (nseg, C, F) with optional injected defects (absolute +-errors on every twiddle /
+    window value; a detrend by the float32-rounded mean)."""
+    rng = np.random.default_rng(seed)
+    C = x.shape[1]
+    F = nfft//2 + 1
+    k = np.arange(nfft//2)
+    tw = np.exp(-2j*np.pi*k/nfft)
+    if twiddle_err:
+        tw = tw + twiddle_err*(rng.choice([-1.0, 1.0], nfft//2) + 1j*rng.choice([-1.0, 1.0], nfft//2))
+    tw = tw.astype(np.complex64)
+    w64 = 0.5 - 0.5*np.cos(2*np.pi*np.arange(nfft)/nfft)
+    w = w64.astype(np.float32)
+    if window_err:
+        w = (w64 + window_err*rng.choice([-1.0, 1.0], nfft)).astype(np.float32)
+    scale = np.float32(1.0/(RATE*np.sum(w64*w64)))
+    segs = np.stack([x[j*hop:j*hop + nfft] for j in range(nseg)])          # (nseg, nfft, C) float32
+    segs = np.moveaxis(segs, 1, 2)                                           # (nseg, C, nfft)
+    mean = segs.astype(np.float64).mean(axis=-1, keepdims=True)
+    if mean32:
+        d = segs - mean.astype(np.float32)                                   # float32 - float32
+    else:
+        d = (segs.astype(np.float64) - mean).astype(np.float32)
+    X = fft32(d*w, tw)[..., :F]
+    P = (X.real*X.real + X.imag*X.imag)*scale
+    P[..., 1:F - 1] *= np.float32(2.0)
+    return P
+
+
+def sequential_direct(x, nfft, hop, nseg):
+    """spec_direct_kernel in float32 on the CPU: the window from the float32 argument 2n/nfft, twiddles from the
+    float32 fraction -2 (k n mod nfft)/nfft, nfft fmaf steps per bin one after another."""
+    F = nfft//2 + 1
+    n = np.arange(nfft)
+    arg = (np.float32(2.0)*n.astype(np.float32))/np.float32(nfft)
+    w = (np.float32(0.5) - np.float32(0.5)*np.cos(np.pi*arg.astype(np.float64)).astype(np.float32))
+    w64 = 0.5 - 0.5*np.cos(2*np.pi*n/nfft)
+    scale = np.float32(1.0/(RATE*np.sum(w64*w64)))
+    segs = np.moveaxis(np.stack([x[j*hop:j*hop + nfft] for j in range(nseg)]), 1, 2)
+    mean = segs.astype(np.float64).mean(axis=-1, keepdims=True)
+    xs = (segs.astype(np.float64) - mean).astype(np.float32)*w               # (nseg, C, nfft)
+    k = np.arange(F)
+    re = np.zeros(xs.shape[:2] + (F,), dtype=np.float32)
+    im = np.zeros_like(re)
+    for i in range(nfft):
+        frac = (np.float32(-2.0)*((k*i) % nfft).astype(np.float32))/np.float32(nfft)
+        ang = np.pi*frac.astype(np.float64)
+        cs, sn = np.cos(ang).astype(np.float32), np.sin(ang).astype(np.float32)
+        xi = xs[..., i:i + 1].astype(np.float64)
+        re = (re + xi*cs).astype(np.float32)                                  # fmaf: one rounding per step
+        im = (im + xi*sn).astype(np.float32)
+    P = (re*re + im*im)*scale
+    P[..., 1:F - 1 if nfft % 2 == 0 else F] *= np.float32(2.0)
+    return P
+
+
+def case(name, nfft, hop=None, nseg=None):
+    hop = hop or max(nfft//2, 1)
+    nseg = nseg or frames_for(nfft)
+    x = sb.family(name, (nseg - 1)*hop + nfft, nfft, RATE, seed=nfft)
+    return x, hop, nseg
+
+
+@pytest.mark.parametrize('name', sb.FAMILIES)
+def test_faithful_float32_within_bound_with_margin(name):
+    worst = []
+    for nfft in SIZES:
+        x, hop, nseg = case(name, nfft)
+        want = reference(x, nfft, hop, nseg)
+        got = emulate(x, nfft, hop, nseg)
+        rho, beta = sb.frame_stats(got, want, nfft)
+        worst.append((nfft, float(rho.max()), float(beta.max())))
+        assert rho.max()*MARGIN <= sb.RHO_MAX, (name, nfft, rho.max())
+        assert beta.max()*MARGIN <= sb.beta_max(nfft), (name, nfft, beta.max())
+        # the dB image of the same PSD passes too
+        with np.errstate(divide='ignore'):
+            db = np.where(got > 1e-20, 10*np.log10(got.astype(np.float64)), -np.inf)
+        assert not sb.check_db(db, got, want, nfft), (name, nfft)
+    print(name, ' '.join('%d:%.2f/%.1f' % w for w in worst))
+
+
+def mutant_stats(name, nfft, **kw):
+    x, hop, nseg = case(name, nfft)
+    want = reference(x, nfft, hop, nseg)
+    got = emulate(x, nfft, hop, nseg, **{k: v for k, v in kw.items() if k in ('twiddle_err', 'window_err', 'mean32')})
+    if kw.get('nyquist'):
+        got[..., -1] *= 2
+    if kw.get('dc'):
+        got[..., 0] *= 2
+    if kw.get('swap'):
+        a = np.sqrt(want[0, 0])
+        level = 20*np.log10(np.maximum(a, 1e-300)/a.max())
+        # of the interior bins within 6 dB of -60 dB, the one that differs most from its upper neighbour
+        near = np.abs(level[1:-2] + 60.0) <= 6.0
+        diff = np.abs(a[1:-2] - a[2:-1])/a[1:-2]
+        if not near.any():
+            return None
+        k = int(np.argmax(np.where(near, diff, -1.0))) + 1
+        got[..., [k, k + 1]] = got[..., [k + 1, k]]
+    rho, beta = sb.frame_stats(got, want, nfft)
+    return float(rho.max()), float(beta.max()), got, want
+
+
+def fails(rho, beta, nfft):
+    return rho > sb.RHO_MAX or beta > sb.beta_max(nfft)
+
+
+@pytest.mark.parametrize('name', sb.FAMILIES)
+def test_twiddle_mutant_fails(name):
+    for nfft in SIZES:
+        rho, beta, _, _ = mutant_stats(name, nfft, twiddle_err=1e-6)
+        assert rho > sb.RHO_MAX, (name, nfft, rho, beta)
+
+
+@pytest.mark.parametrize('name', ['tones', 'bandpass', 'chirp', 'synth'])
+def test_window_mutant_fails(name):
+    for nfft in SIZES:
+        rho, beta, _, _ = mutant_stats(name, nfft, window_err=4e-6)
+        assert fails(rho, beta, nfft), (name, nfft, rho, beta)
+
+
+def test_edge_bin_mutants_fail():
+    """A doubled Nyquist bin (its component at -60 dB) and a doubled DC bin, on the edge-bin family."""
+    for nfft in SIZES:
+        for kw in ({'nyquist': True}, {'dc': True}):
+            rho, beta, _, _ = mutant_stats('edges', nfft, **kw)
+            assert fails(rho, beta, nfft), (nfft, kw, rho, beta)
+
+
+@pytest.mark.parametrize('name', ['tones', 'bandpass', 'synth', 'edges'])
+def test_swapped_bins_fail(name):
+    """(Not on the chirp: its -60 dB bins lie on a smooth skirt, neighbours within a few per cent of each other.)"""
+    tried = 0
+    for nfft in SIZES:
+        res = mutant_stats(name, nfft, swap=True)
+        if res is None:
+            continue                                        # (no bin near -60 dB in a short window of this family)
+        tried += 1
+        assert res[1] > sb.beta_max(nfft), (name, nfft, res[0], res[1])
+    assert tried >= 8, tried
+
+
+def test_float32_mean_detrend_fails():
+    for nfft in SIZES:
+        rho, beta, _, _ = mutant_stats('offset', nfft, mean32=True)
+        assert fails(rho, beta, nfft), (nfft, rho, beta)
+
+
+def test_rel_err_accepts_the_twiddle_mutant():
+    """The gap the bound closes: the per-frame peak-relative metric lets +-1e-6 twiddles through."""
+    for nfft in (64, 1024, 16384):
+        rho, beta, got, want = mutant_stats('tones', nfft, twiddle_err=1e-6)
+        assert rho > sb.RHO_MAX
+        for j in range(got.shape[0]):
+            for c in range(got.shape[1]):
+                assert rel_err(got[j, c], want[j, c]) < 1e-4
+
+
+DIRECT = [24, 1000, 3000, 12000]
+
+
+@pytest.mark.parametrize('nfft', DIRECT)
+def test_direct_dft_bound(nfft):
+    """The sequential float32 DFT within the sqrt(nfft) bound with margin (one frame: the emulation is O(nfft^2))."""
+    for name in sb.FAMILIES if nfft < 10000 else ('tones', 'edges', 'offset'):
+        x = sb.family(name, nfft, nfft, RATE, seed=nfft)
+        want = reference(x, nfft, nfft, 1)
+        got = sequential_direct(x, nfft, nfft, 1)
+        rho, beta = sb.frame_stats(got, want, nfft, direct=True)
+        assert rho.max()*MARGIN <= sb.RHO_MAX, (name, nfft, rho.max())
+        assert beta.max()*MARGIN <= sb.beta_max(nfft), (name, nfft, beta.max())
+        print('direct', nfft, name, '%.2f %.2f' % (rho.max(), beta.max()))
