@@ -89,6 +89,9 @@ _SIGNATURES = {
     'hipdsp_memcpy_h2d': ([_vp, _vp, _vp, _sz], _int),
     'hipdsp_memcpy_d2h': ([_vp, _vp, _vp, _sz], _int),
     'hipdsp_memcpy_d2d': ([_vp, _vp, _vp, _sz], _int),
+    'hipdsp_host_malloc': ([_vp, _sz, _pp], _int),
+    'hipdsp_host_free': ([_vp, _vp], _int),
+    'hipdsp_memcpy_h2d_async': ([_vp, _vp, _vp, _sz], _int),
     'hipdsp_memcpy2d_d2d': ([_vp, _vp, _sz, _vp, _sz, _sz, _sz], _int),
     'hipdsp_event_create': ([_vp, _pp], _int),
     'hipdsp_event_destroy': ([_vp, _vp], _int),
@@ -127,6 +130,7 @@ _SIGNATURES = {
     'hipdsp_unwrap': ([_vp, _vp, _i64, _i64, _i64, _dbl, _dbl, _int, _int, _vp, _i64], _int),
     'hipdsp_pcm_unpack': ([_vp, _vp, _int, _i64, _i64, _dbl, _vp, _i64], _int),
     'hipdsp_minmax_decimate': ([_vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _i64], _int),
+    'hipdsp_pcm_minmax': ([_vp, _vp, _int, _i64, _i64, _i64, _dbl, _dbl, _dbl, _int, _int, _vp, _i64], _int),
     'hipdsp_mean_spectrum_db': ([_vp, _vp, _i64, _i64, _i64, _dbl, _dbl, _dbl, _vp], _int),
     'hipdsp_comm_unique_id': ([_vp], _int),
     'hipdsp_comm_create': ([_vp, _vp, _int, _int, _pp], _int),

@@ -269,6 +269,7 @@ class WavLoader(BufferedArray):
         if self._wav.getcomptype() != 'NONE' or self._wav.getsampwidth() not in (2, 3, 4):
             raise ValueError('only uncompressed 16/24/32-bit PCM WAV files are supported')
         self.filepath = path
+        self.file_paths = [path]       # the attribute audian's CompressedData reads (one file per loader here)
         self.sample_bytes = self._wav.getsampwidth()
         self.scale = 1.0/float(1 << (8*self.sample_bytes - 1))
         self.rate = float(self._wav.getframerate())

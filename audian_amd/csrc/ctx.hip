@@ -453,6 +453,38 @@ int hipdsp_memcpy_h2d(hipdsp_ctx *ctx, void *dst, const void *host_src, size_t b
     return HIPDSP_OK;
 }
 
+int hipdsp_host_malloc(hipdsp_ctx *ctx, size_t bytes, void **host_ptr)
+{
+    HD_REQUIRE(ctx != nullptr && host_ptr != nullptr, "NULL argument");
+    *host_ptr = nullptr;
+    if (bytes == 0) return HIPDSP_OK;
+    HD_CHECK_HIP(hipSetDevice(ctx->device));
+    if (hipHostMalloc(host_ptr, bytes, hipHostMallocDefault) != hipSuccess || *host_ptr == nullptr) {
+        (void)hipGetLastError();
+        *host_ptr = nullptr;
+        hipdsp_set_error("hipHostMalloc of %zu bytes failed", bytes);
+        return HIPDSP_ERR_NOMEM;
+    }
+    return HIPDSP_OK;
+}
+
+int hipdsp_host_free(hipdsp_ctx *ctx, void *host_ptr)
+{
+    HD_REQUIRE(ctx != nullptr, "ctx is NULL");
+    if (host_ptr != nullptr) HD_CHECK_HIP(hipHostFree(host_ptr));
+    return HIPDSP_OK;
+}
+
+int hipdsp_memcpy_h2d_async(hipdsp_ctx *ctx, void *dst, const void *host_src, size_t bytes)
+{
+    HD_REQUIRE(ctx != nullptr, "ctx is NULL");
+    if (bytes) {
+        HD_REQUIRE(dst != nullptr && host_src != nullptr, "NULL data pointer");
+        HD_CHECK_HIP(hipMemcpyAsync(dst, host_src, bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    return HIPDSP_OK;
+}
+
 int hipdsp_memcpy_d2h(hipdsp_ctx *ctx, void *host_dst, const void *src, size_t bytes)
 {
     HD_REQUIRE(ctx != nullptr, "ctx is NULL");

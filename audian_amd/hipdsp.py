@@ -447,6 +447,50 @@ def pcm_unpack(ctx, pcm_tc, sample_bytes, frames, channels, scale, dst, dst_pitc
                                 float(scale), _p(dst), int(dst_pitch)))
 
 
+def pcm_minmax(ctx, pcm_tc, sample_bytes, frames, channels, step, scale, out_rc, out_pitch,
+               unwrap_thresh=0.0, ampl_max=1.0, clips=False, down_scale=False):
+    """Full-trace overview of a block of interleaved PCM (hipdsp_pcm_minmax): out_rc gets float64
+    (2*ceil(frames/step), channels) rows of min, max, min, ... with row pitch out_pitch elements."""
+    check(lib.hipdsp_pcm_minmax(ctx.handle, _p(pcm_tc), int(sample_bytes), int(frames), int(channels), int(step),
+                                float(scale), float(unwrap_thresh), float(ampl_max), int(bool(clips)),
+                                int(bool(down_scale)), _p(out_rc), int(out_pitch)))
+
+
+class HostBuffer:
+    """Page-locked host memory (hipdsp_host_malloc) seen as a NumPy uint8 array: the source of
+    hipdsp_memcpy_h2d_async."""
+
+    def __init__(self, ctx, nbytes):
+        self.ctx = ctx
+        self.nbytes = int(nbytes)
+        p = ctypes.c_void_p()
+        check(lib.hipdsp_host_malloc(ctx.handle, self.nbytes, ctypes.byref(p)))
+        self.ptr = p.value or 0
+        if self.nbytes:
+            self.array = np.ctypeslib.as_array((ctypes.c_uint8*self.nbytes).from_address(self.ptr))
+        else:
+            self.array = np.zeros(0, dtype=np.uint8)
+
+    def free(self):
+        if self.ptr:
+            self.array = None
+            lib.hipdsp_host_free(self.ctx.handle, ctypes.c_void_p(self.ptr))
+            self.ptr = 0
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def memcpy_h2d_async(ctx, dst, host_src, nbytes):
+    """Copy `nbytes` from page-locked host memory (a HostBuffer or its address) to the device, ordered on
+    the context's stream and NOT waited for."""
+    src = host_src.ptr if isinstance(host_src, HostBuffer) else int(host_src)
+    check(lib.hipdsp_memcpy_h2d_async(ctx.handle, _p(dst), ctypes.c_void_p(src), int(nbytes)))
+
+
 def minmax_decimate(ctx, x, x_pitch, channels, start, stop, step, out, out_pitch):
     check(lib.hipdsp_minmax_decimate(ctx.handle, _p(x), int(x_pitch), int(channels), int(start),
                                      int(stop), int(step), _p(out), int(out_pitch)))

@@ -156,6 +156,14 @@ int hipdsp_memset(hipdsp_ctx *ctx, void *dptr, int value, size_t bytes);
 int hipdsp_memcpy_h2d(hipdsp_ctx *ctx, void *dst, const void *host_src, size_t bytes);
 int hipdsp_memcpy_d2h(hipdsp_ctx *ctx, void *host_dst, const void *src, size_t bytes);
 int hipdsp_memcpy_d2d(hipdsp_ctx *ctx, void *dst, const void *src, size_t bytes);
+/* Page-locked host staging (CompressedData's block reader, audian_amd/compresseddata.py): _host_malloc returns
+ * `bytes` of pinned host memory (hipHostMalloc; the context names the device), _host_free gives it back.  Unlike
+ * hipdsp_memcpy_h2d, hipdsp_memcpy_h2d_async does NOT wait: the copy is ordered on the context's stream and
+ * `host_src` must be page-locked (from hipdsp_host_malloc) and left untouched until the stream has passed the
+ * copy (hipdsp_event_record + a wait, or hipdsp_ctx_synchronize). */
+int hipdsp_host_malloc(hipdsp_ctx *ctx, size_t bytes, void **host_ptr);
+int hipdsp_host_free(hipdsp_ctx *ctx, void *host_ptr);
+int hipdsp_memcpy_h2d_async(hipdsp_ctx *ctx, void *dst, const void *host_src, size_t bytes);
 /* `height` rows of `width` bytes between pitched device blocks (ring-buffer recycling
  * of the device mirror, buffereddata.py:87). */
 int hipdsp_memcpy2d_d2d(hipdsp_ctx *ctx, void *dst, size_t dst_pitch, const void *src,
@@ -478,6 +486,23 @@ int hipdsp_unwrap(hipdsp_ctx *ctx, const float *x, int64_t x_pitch, int64_t chan
  * integers instead of float64 cuts the PCIe volume of the raw slab 2.7-4x. */
 int hipdsp_pcm_unpack(hipdsp_ctx *ctx, const void *pcm_tc, int sample_bytes, int64_t frames,
                       int64_t channels, double scale, float *dst, int64_t dst_pitch);
+
+/* Full-trace overview straight from the file's PCM (CompressedData.start / down_sample_worker,
+ * src/audian/compresseddata.py:25-52, 102-113): the min/max envelope of interleaved little-endian signed PCM
+ * (frames, channels) of 2, 3 or 4 bytes per sample, in the reference's layout: out_rc is float64
+ * (2*nseg, channels) with row pitch out_pitch (elements), nseg = ceil(frames/step), row 2j the minimum and row
+ * 2j+1 the maximum of frames [j*step, min((j+1)*step, frames)).  One read of the PCM bytes (hipdsp_pcm_unpack +
+ * hipdsp_minmax_decimate move about 10 B per int16 sample).  Bit-exact:
+ *   unwrap_thresh <= 1e-3: the values are int * scale in float64 (reduced as integers, scaled once per segment);
+ *   else: hipdsp_unwrap's arithmetic on x = (float)(int * scale) -- events beyond +-unwrap_thresh shift by
+ *         -+2*ampl_max from zero at the call's first frame, then clip to +-ampl_max (clips) or halve (down_scale) --
+ *         and the min/max of those float32 values, widened.  The PCM is read twice (count, then reduce).
+ * Any step >= 1 (step = 1: twice as many output rows as frames; step > frames: one segment).  Frames of at most
+ * 16384 bytes (channels * sample_bytes; HIPDSP_ERR_UNSUPPORTED beyond).  Uses the context scratch (8 bytes per
+ * segment and channel, plus 4 bytes per channel and run of frames a thread walks, with unwrap). */
+int hipdsp_pcm_minmax(hipdsp_ctx *ctx, const void *pcm_tc, int sample_bytes, int64_t frames, int64_t channels,
+                      int64_t step, double scale, double unwrap_thresh, double ampl_max, int clips, int down_scale,
+                      double *out_rc, int64_t out_pitch);
 
 /* Power spectrum of the visible window (SpectrogramPlot.update_plot,
  * spectrogramplot.py:158-160):
