@@ -132,6 +132,8 @@ _SIGNATURES = {
     'hipdsp_minmax_decimate': ([_vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _i64], _int),
     'hipdsp_pcm_minmax': ([_vp, _vp, _int, _i64, _i64, _i64, _dbl, _dbl, _dbl, _int, _int, _vp, _i64], _int),
     'hipdsp_mean_spectrum_db': ([_vp, _vp, _i64, _i64, _i64, _dbl, _dbl, _dbl, _vp], _int),
+    'hipdsp_band_power': ([_vp, _vp, _i64, _i64, _i64, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _int, _dbl, _int, _dbl, _dbl,
+                          _vp, _i64, _i64], _int),
     'hipdsp_comm_unique_id': ([_vp], _int),
     'hipdsp_comm_create': ([_vp, _vp, _int, _int, _pp], _int),
     'hipdsp_comm_destroy': ([_vp, _vp], _int),
@@ -141,6 +143,8 @@ _SIGNATURES = {
 }
 
 for _name, (_args, _res) in _SIGNATURES.items():
+    if os.environ.get('AUDIAN_AMD_LIB') and not hasattr(lib, _name):
+        continue                   # another, older build for an A/B: it simply lacks the newer entry points
     _fn = getattr(lib, _name)      # AttributeError here = header and library disagree
     _fn.argtypes = _args
     _fn.restype = _res

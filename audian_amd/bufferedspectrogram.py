@@ -34,6 +34,35 @@ def hop_for(nfft, overlap_frac):
     return int(min(max(np.round(nfft*(1 - overlap_frac)), 1), nfft))
 
 
+def band_bins(fmin, fmax, fresolution, nfreq):
+    """(k0, k1): the bins k of an `nfreq`-bin spectrum with fmin <= k*fresolution <= fmax, clipped to [0, nfreq];
+    fmax None: up to the last (Nyquist) bin.  k0 == k1 when no bin lies in the band."""
+    fres, F = float(fresolution), int(nfreq)
+    fmin = 0.0 if fmin is None else float(fmin)
+    if fmin <= 0:
+        k0 = 0
+    elif fmin > (F - 1)*fres:
+        k0 = F
+    else:
+        k0 = int(np.ceil(fmin/fres))
+        while k0 > 0 and (k0 - 1)*fres >= fmin:
+            k0 -= 1
+        while k0 < F and k0*fres < fmin:
+            k0 += 1
+    if fmax is None or float(fmax) >= (F - 1)*fres:
+        k1 = F
+    elif fmax < 0:
+        k1 = 0
+    else:
+        k = int(np.floor(float(fmax)/fres))
+        while k + 1 < F and (k + 1)*fres <= fmax:
+            k += 1
+        while k >= 0 and k*fres > fmax:
+            k -= 1
+        k1 = k + 1
+    return k0, max(k0, k1)
+
+
 class BufferedSpectrogram(BufferedData):
     """Same constructor and attributes as audian's class (bufferedspectrogram.py:14-29):
     nfft / hop / overlap_frac, frequencies, fresolution, tresolution, spec_rect, use_spec, init."""
@@ -202,6 +231,34 @@ class BufferedSpectrogram(BufferedData):
         power = decibel(np.mean(self.buffer[a:b, channel, :], axis=0))
         power[power < floor_db] = floor_db
         return power
+
+    def band_powers(self, bands_hz, i0, i1, log=False, min_power=1e-20):
+        """The power inside several frequency bands at once: fresolution * sum over the bins of each (fmin, fmax) of
+        `bands_hz` (Hz, fmax None = Nyquist; the bins of band_bins()) for frames [i0, i1) (absolute frame indices
+        inside the current buffer), decibel of that with `log`.  Returns float32 (len(bands), channels, i1 - i0).
+        With a valid device mirror one pass over the slab serves all bands (hipdsp_band_power, 16 bands per launch):
+        a bin that lies in several bands is read once and only the result crosses PCIe."""
+        from . import hipdsp
+        from .buffereddata import _covers
+        F = self.nfft//2 + 1
+        a, b = int(i0) - self.offset, int(i1) - self.offset
+        n = len(self._hostbuf)
+        if a < 0 or b > n or b < a:
+            raise IndexError('range outside the loaded buffer')
+        bins = [band_bins(f0, f1, self.fresolution, F) for f0, f1 in bands_hz]
+        m = b - a
+        if m == 0 or not bins:
+            return np.zeros((len(bins), self.channels, m), dtype=np.float32)
+        if self._dev is not None and _covers(self._dev_valid, a, b):
+            out = hipdsp.DeviceArray(self.ctx, (len(bins), self.channels, m), np.float32)
+            for j in range(0, len(bins), 16):
+                hipdsp.band_power(self.ctx, self._dev.view(a*F, (1,)), self._pitch(), self.channels, m, F,
+                                  bins[j:j + 16], self.fresolution, out.view(j*self.channels*m, (1,)), db=log,
+                                  min_power=min_power)
+            return out.to_host()
+        slab = np.asarray(self.buffer[a:b], dtype=np.float64)
+        power = np.stack([self.fresolution*np.sum(slab[:, :, k0:k1], axis=2).T for k0, k1 in bins])
+        return (decibel(power, 1.0, min_power) if log else power).astype(np.float32)
 
     def estimate_noiselevels(self, channel):
         """Colour range for the spectrogram image (bufferedspectrogram.py:109-126): 95th

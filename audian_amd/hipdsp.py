@@ -502,6 +502,19 @@ def mean_spectrum_db(ctx, spec_tf, nfreq, i0, i1, out, ref_power=1.0, min_power=
                                       float(ref_power), float(min_power), float(floor_db), _p(out)))
 
 
+def band_power(ctx, spec, spec_pitch, channels, frames, nfreq, bands, scale, out, db=False, ref_power=1.0,
+               min_power=1e-20, out_pitch=0, out_band_pitch=0):
+    """out[b, c, t] = scale * sum(spec[c, t, k0:k1]) for every (k0, k1) of `bands` (bin ranges; at most 16), float32,
+    decibel of that with db (hipdsp_band_power): one pass over the bins the bands cover."""
+    bands = [(int(k0), int(k1)) for k0, k1 in bands]
+    k0 = (ctypes.c_int64*max(1, len(bands)))(*[b[0] for b in bands])
+    k1 = (ctypes.c_int64*max(1, len(bands)))(*[b[1] for b in bands])
+    _count('band_power')
+    check(lib.hipdsp_band_power(ctx.handle, _p(spec), int(spec_pitch), int(channels), int(frames), int(nfreq), k0, k1,
+                                len(bands), float(scale), int(bool(db)), float(ref_power), float(min_power), _p(out),
+                                int(out_pitch), int(out_band_pitch)))
+
+
 def memcpy2d(ctx, dst, dst_pitch_bytes, src, src_pitch_bytes, width_bytes, height):
     check(lib.hipdsp_memcpy2d_d2d(ctx.handle, _p(dst), int(dst_pitch_bytes), _p(src),
                                   int(src_pitch_bytes), int(width_bytes), int(height)))

@@ -513,6 +513,29 @@ int hipdsp_mean_spectrum_db(hipdsp_ctx *ctx, const float *spec_tf, int64_t nfreq
                             int64_t i1, double ref_power, double min_power, double floor_db,
                             float *out);
 
+/* Band power: the derived trace whose source is the spectrogram, the reference's open plug-in test "Envelope from
+ * visible frequency range of spectrogram" (README.md:63).  spec is the planar slab the spectrogram entry points write,
+ * (channels, frames, nfreq) float32 with spec_pitch elements between channels (0 = compact); for every band b, channel
+ * c and frame t
+ *   out[b*out_band_pitch + c*out_pitch + t] = scale * sum(spec[c, t, k0[b]:k1[b]])            (float32)
+ * (out_pitch 0 = frames, out_band_pitch 0 = channels*out_pitch); with db != 0 the value stored is
+ * decibel(that, ref_power, min_power) in exactly hipdsp_decibel's arithmetic (-inf at or below min_power).  With
+ * scale = the bin width in Hz this is the integral of the PSD over the band, in the signal's squared unit.
+ * host_k0 / host_k1 are HOST arrays of n_bands bin ranges, 0 <= k0 <= k1 <= nfreq (k0 == k1: an empty band, 0 or -inf);
+ * they travel to the kernel by value: no upload, no host synchronisation, legal inside hipdsp_graph_begin/end.  Up to
+ * 16 bands per call (more: HIPDSP_ERR_UNSUPPORTED), all served by ONE pass: of every row only the bins the union of
+ * the bands covers are read, and a bin that lies in several bands is read once.  A multi-band call gives bit for bit
+ * what one call per band gives.  NaN and +-inf propagate as in np.sum, to their own frame's value only.  frames == 0
+ * or channels == 0: nothing is written.  No alignment is assumed (rows of nfreq = nfft/2 + 1 floats start at any
+ * 4-byte address); at most 65535 channels and 2^24 - 1 frames per call (2^31 - 1 with nfreq <= 256).
+ * Accuracy: the bins are summed in float64 and the scaled sum is rounded to float32 once.  A float64 sum of at most
+ * 2^18 + 1 float32 terms of one sign is off by less than 2^-34 relative, so for non-negative input the linear result
+ * is within 1 float32 ulp of float32(scale * S), S the exact sum of the bins. */
+int hipdsp_band_power(hipdsp_ctx *ctx, const float *spec, int64_t spec_pitch, int64_t channels,
+                      int64_t frames, int64_t nfreq, const int64_t *host_k0, const int64_t *host_k1,
+                      int n_bands, double scale, int db, double ref_power, double min_power,
+                      float *out, int64_t out_pitch, int64_t out_band_pitch);
+
 /* ---- multi-GPU exchange ---------------------------------------- */
 
 /* One process per GPU, channels sharded in contiguous blocks of the planar layout, so

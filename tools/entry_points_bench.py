@@ -118,6 +118,26 @@ for row in zip(*tables):
         ms = best[b['name']]
         logs[b['name']].append(f'{name:78s} {ms:8.3f} ms {nbytes/ms/1e6:7.0f} GB/s')
     print(logs[builds[-1]['name']][-1] + ('' if len(builds) == 1 else '    | ' + '  '.join(f"{b['name']} {best[b['name']]:.3f}" for b in builds[:-1])), flush=True)
+# ---- hipdsp_band_power over configs[2]'s PSD slab (tools/band_power_bench.py has the other slabs and band sets).  A build
+# from before the entry point existed has no such lines: the gate lists them as new.
+nfft, hop = 2048, 1024
+F, nd = nfft//2 + 1, (T + hop - 1)//hop
+for b in builds:
+    h, ctx = b['h'], b['ctx']
+    if not hasattr(h.lib, 'hipdsp_band_power'):
+        continue
+    df, ds, de = b['buf']['df'], b['buf']['ds'], b['buf']['de']
+    h.sosfilt(ctx, b['bp2'], b['buf']['dx'], T, df, T, C, T, 0)
+    h.spectrogram(ctx, df, T, C, T, nfft, hop, rate, ds, nd)
+    ctx.synchronize()
+    for name, bands in (('the full band', [(0, F)]), ('a 64-bin band', [(341, 405)]),
+                        ('4 disjoint bands of 64 bins in one call', [(j*256 + 1, j*256 + 65) for j in range(4)])):
+        nbytes = 4.0*C*nd*(sum(k1 - k0 for k0, k1 in bands) + len(bands))
+        ms = min(timed(b, lambda: h.band_power(ctx, ds, 0, C, nd, F, bands, rate/nfft, de), 5) for _ in range(rounds))
+        ctx.synchronize()
+        logs[b['name']].append(f'{"hipdsp_band_power over the PSD 2048/1024, " + name:78s} {ms:8.3f} ms {nbytes/ms/1e6:7.0f} GB/s')
+        if b is builds[-1]:
+            print(logs[b['name']][-1], flush=True)
 prefix = os.environ.get('OUT_PREFIX')
 if prefix:
     for name, lines in logs.items():
