@@ -188,3 +188,24 @@ def butter_sos(order, Wn, btype, fs):
         raise ValueError(f"'{btype}' is not a filter type used by audian")
     z, p, k = _bilinear(z, p, k)
     return zpk_to_sos(z, p, k)
+
+
+MAX_FIR_TAPS = 4097        # longest kernel a FIR plan holds (hipdsp_firplan_set)
+
+
+def gabor_kernels(rate, sigma, freqs, phase=0.0):
+    """The usual bank for a kernel-filter feature expansion: row k is exp(-t^2/(2 sigma^2)) cos(2 pi freqs[k] t + phase)
+    on t = (j - (L-1)/2)/rate, L = 2*ceil(4 sigma rate) + 1 taps (four standard deviations to either side), scaled to
+    unit L2 norm.  `sigma` in seconds, `freqs` in Hz.  Returns (len(freqs), L) float64; ValueError when L exceeds
+    the 4097 taps a FIR plan holds."""
+    half = int(np.ceil(4.0*sigma*rate))
+    n_taps = 2*half + 1
+    if n_taps > MAX_FIR_TAPS:
+        raise ValueError(f'sigma = {sigma} s at {rate} Hz needs {n_taps} taps, more than {MAX_FIR_TAPS}')
+    t = np.arange(-half, half + 1)/float(rate)
+    freqs = np.atleast_1d(np.asarray(freqs, dtype=np.float64))
+    rows = np.exp(-t**2/(2.0*sigma**2))[None, :]*np.cos(2.0*np.pi*freqs[:, None]*t[None, :] + phase)
+    norm = np.sqrt(np.sum(rows**2, axis=1, keepdims=True))
+    if np.any(norm == 0.0):
+        raise ValueError('a kernel of the bank is identically zero')
+    return rows/norm

@@ -252,6 +252,58 @@ class SosPlan:
             pass
 
 
+class FirPlan:
+    """Device-resident taps and thresholds of up to 16 FIR kernels of one length (hipdsp_firplan_* in hip_dsp.h)."""
+
+    def __init__(self, ctx, taps=None, thresholds=None):
+        self.ctx = ctx
+        h = ctypes.c_void_p()
+        check(lib.hipdsp_firplan_create(ctx.handle, ctypes.byref(h)))
+        self._h = h
+        self.n_kernels = self.n_taps = 0
+        if taps is not None:
+            self.set(taps, thresholds)
+
+    @staticmethod
+    def _tables(taps, thresholds):
+        taps = np.ascontiguousarray(np.atleast_2d(np.asarray(taps, dtype=np.float64)))
+        if taps.ndim != 2:
+            raise ValueError('taps must be shape (n_kernels, n_taps)')
+        if thresholds is not None:
+            thresholds = np.ascontiguousarray(np.broadcast_to(np.asarray(thresholds, dtype=np.float64), (len(taps),)))
+        return taps, thresholds
+
+    def _call(self, fn, taps, thresholds):
+        taps, thr = self._tables(taps, thresholds)
+        check(fn(self.ctx.handle, self._h, ctypes.c_void_p(taps.ctypes.data), taps.shape[0], taps.shape[1],
+                 ctypes.c_void_p(thr.ctypes.data if thr is not None else 0)))
+        self.n_kernels, self.n_taps = taps.shape
+
+    def set(self, taps, thresholds=None):
+        self._call(lib.hipdsp_firplan_set, taps, thresholds)
+
+    def set_host(self, taps, thresholds=None):
+        self._call(lib.hipdsp_firplan_set_host, taps, thresholds)
+
+    def upload(self):
+        check(lib.hipdsp_firplan_upload(self.ctx.handle, self._h))
+
+    @property
+    def handle(self):
+        return self._h
+
+    def close(self):
+        if self._h is not None and self._h.value:
+            lib.hipdsp_firplan_destroy(self.ctx.handle, self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Comm:
     """RCCL communicator behind the C ABI (hipdsp_comm_*): rank 0 calls
     `Comm.unique_id()` and ships the 128 bytes to the other ranks."""
@@ -513,6 +565,16 @@ def band_power(ctx, spec, spec_pitch, channels, frames, nfreq, bands, scale, out
     check(lib.hipdsp_band_power(ctx.handle, _p(spec), int(spec_pitch), int(channels), int(frames), int(nfreq), k0, k1,
                                 len(bands), float(scale), int(bool(db)), float(ref_power), float(min_power), _p(out),
                                 int(out_pitch), int(out_band_pitch)))
+
+
+def fir_bank(ctx, plan, x, x_pitch, channels, frames, first, step, n_out, out, rectify=False, out_pitch=0,
+             out_kernel_pitch=0):
+    """out[k, c, i] = sum_j taps[k, j] * x[c, first + i*step + (L-1)//2 - j] for every kernel of `plan`, x zero outside
+    [0, frames); max(. - threshold[k], 0) with rectify (hipdsp_fir_bank): float32 products on the matrix cores."""
+    _count('fir_bank')
+    check(lib.hipdsp_fir_bank(ctx.handle, _plan(plan), _p(x), int(x_pitch), int(channels), int(frames), int(first),
+                              int(step), int(n_out), int(bool(rectify)), _p(out), int(out_pitch),
+                              int(out_kernel_pitch)))
 
 
 def memcpy2d(ctx, dst, dst_pitch_bytes, src, src_pitch_bytes, width_bytes, height):

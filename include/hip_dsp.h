@@ -45,6 +45,7 @@ extern "C" {
 
 typedef struct hipdsp_ctx hipdsp_ctx;
 typedef struct hipdsp_sosplan hipdsp_sosplan;
+typedef struct hipdsp_firplan hipdsp_firplan;
 
 /* ---- library / context ------------------------------------------------- */
 
@@ -535,6 +536,60 @@ int hipdsp_band_power(hipdsp_ctx *ctx, const float *spec, int64_t spec_pitch, in
                       int64_t frames, int64_t nfreq, const int64_t *host_k0, const int64_t *host_k1,
                       int n_bands, double scale, int db, double ref_power, double min_power,
                       float *out, int64_t out_pitch, int64_t out_band_pitch);
+
+/* ---- FIR kernel bank ("feature expansion (kernel filter)") ----------------- */
+
+/* A plan holds, in device memory, the taps and thresholds of up to 16 FIR kernels of one common length, as
+ * hipdsp_sosplan holds an SOS table: hipdsp_firplan_set is hipdsp_firplan_set_host (rounds and lays the taps out in
+ * pinned host memory, no stream work) followed by hipdsp_firplan_upload (an async copy on the stream, which may be
+ * captured), so a captured hipGraph replays under new kernels.  hipdsp_fir_bank reads n_kernels and n_taps from
+ * the host side of the plan at call time (a captured call keeps those of capture time: replay it only under tap sets
+ * of the same counts), and returns HIPDSP_ERR_INVALID while they differ from what was last uploaded, i.e. after a
+ * hipdsp_firplan_set_host with new counts and no upload.  With equal counts the device keeps the previously uploaded
+ * taps until the next upload.  hipdsp_firplan_set_host waits for the last upload enqueued
+ * outside a capture before it rewrites the pinned block; a replayed graph's copy is not known to it, so the caller
+ * synchronises the stream between a replay and the next hipdsp_firplan_set_host.
+ * host_taps: (n_kernels, n_taps) float64, row k = kernel k; host_threshold: n_kernels float64, or NULL for zeros.
+ * 1 <= n_kernels <= 16 and 1 <= n_taps <= 4097: larger counts give HIPDSP_ERR_UNSUPPORTED, zero or negative ones
+ * HIPDSP_ERR_INVALID. */
+int hipdsp_firplan_create(hipdsp_ctx *ctx, hipdsp_firplan **out);
+int hipdsp_firplan_destroy(hipdsp_ctx *ctx, hipdsp_firplan *plan);
+int hipdsp_firplan_set(hipdsp_ctx *ctx, hipdsp_firplan *plan, const double *host_taps, int n_kernels,
+                       int n_taps, const double *host_threshold);
+int hipdsp_firplan_set_host(hipdsp_ctx *ctx, hipdsp_firplan *plan, const double *host_taps, int n_kernels,
+                            int n_taps, const double *host_threshold);
+int hipdsp_firplan_upload(hipdsp_ctx *ctx, hipdsp_firplan *plan);
+
+/* One feature trace per kernel of the plan.  With x[c, i] = 0 for i outside [0, frames), h = taps[k], L = n_taps:
+ *     y[k, c, t] = sum_{j=0}^{L-1} h[j] * x[c, t + (L-1)/2 - j]     (integer division; for frames >= L this is
+ *                                                                     np.convolve(x[c], h, 'same')[t])
+ *     out[k*out_kernel_pitch + c*out_pitch + i] = y[k, c, first + i*step],   i < n_out
+ * and with rectify != 0  max(y - threshold[k], 0)  (a NaN stays NaN, as np.maximum).
+ * x is planar float32 with x_pitch floats per channel (0 = frames); out_pitch 0 means n_out, out_kernel_pitch 0
+ * means channels*out_pitch (the layout of hipdsp_band_power).  Any first >= 0 is allowed, also first + i*step >=
+ * frames: such windows are partly or wholly zeros.  step >= 1; a negative first or size is HIPDSP_ERR_INVALID; x and
+ * out must not overlap (HIPDSP_ERR_INVALID); n_out == 0 or channels == 0 writes nothing; frames == 0 gives zeros
+ * (rectified zeros).  At most 65535 channels and 2^36 outputs per call; index arithmetic is 64-bit.  Legal inside
+ * hipdsp_graph_begin/end (nothing is allocated or configured by the call).
+ *
+ * Arithmetic contract.  Taps and thresholds are rounded to float32 once, on the host.  The products run on the
+ * f32-input matrix core (v_mfma_f32_16x16x4_f32): every output is a float32 sum of float32 products with one rounding
+ * per step -- an fmaf chain over the taps in some fixed order, the same for every output, or a regrouping of one.
+ * For any summation order that gives, with u = 2^-24, n = L + 2 and M = sum_j |h[j]| * |x[..]| (the same window with
+ * absolute values),
+ *     |out - y_float64| <= n*u / (1 - n*u) * M,
+ * and with rectify  (n+1)*u / (1 - (n+1)*u) * (M + |threshold|).  When every tap, sample and partial sum is an integer
+ * below 2^24 in magnitude the result is therefore exact.
+ * Determinism: the value for kernel k does not depend on which other kernels ride in the call (the mapping is chosen
+ * by n_taps and step, never by n_kernels): a 16-kernel call gives bit for bit what 16 one-kernel calls give; the same
+ * call gives the same bits twice.
+ * Non-finite samples: an output is non-finite if its L-sample window contains a non-finite sample (without rectify;
+ * max(-inf, 0) is 0); zero padding of the taps (to a multiple of 4) may carry that at most 16 samples further; an
+ * output whose window is at least 16 samples clear of every non-finite sample equals what it is without that
+ * sample, and other channels are not affected. */
+int hipdsp_fir_bank(hipdsp_ctx *ctx, const hipdsp_firplan *plan, const float *x, int64_t x_pitch,
+                    int64_t channels, int64_t frames, int64_t first, int64_t step, int64_t n_out, int rectify,
+                    float *out, int64_t out_pitch, int64_t out_kernel_pitch);
 
 /* ---- multi-GPU exchange ---------------------------------------- */
 

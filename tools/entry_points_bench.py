@@ -138,6 +138,20 @@ for b in builds:
         logs[b['name']].append(f'{"hipdsp_band_power over the PSD 2048/1024, " + name:78s} {ms:8.3f} ms {nbytes/ms/1e6:7.0f} GB/s')
         if b is builds[-1]:
             print(logs[b['name']][-1], flush=True)
+# ---- hipdsp_fir_bank: 16 kernels of 257 taps over the envelope, one frame per millisecond (tools/fir_bank_bench.py has the
+# other kernel lengths and steps)
+for b in builds:
+    h, ctx = b['h'], b['ctx']
+    if not hasattr(h.lib, 'hipdsp_fir_bank'):
+        continue
+    n_out = -(-T//96)
+    plan = h.FirPlan(ctx, np.random.default_rng(7).standard_normal((16, 257))/16.0)
+    nbytes = 4.0*S + 4.0*16*C*n_out
+    ms = min(timed(b, lambda: h.fir_bank(ctx, plan, b['buf']['df'], T, C, T, 0, 96, n_out, b['buf']['ds']), 5) for _ in range(rounds))
+    ctx.synchronize()
+    logs[b['name']].append(f'{"hipdsp_fir_bank, 16 kernels of 257 taps, step 96":78s} {ms:8.3f} ms {nbytes/ms/1e6:7.0f} GB/s')
+    if b is builds[-1]:
+        print(logs[b['name']][-1], flush=True)
 prefix = os.environ.get('OUT_PREFIX')
 if prefix:
     for name, lines in logs.items():
