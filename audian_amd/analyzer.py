@@ -1,0 +1,251 @@
+"""Region analysis: audian's ``Analyzer`` plug-in surface (``src/audian/analyzer.py``,
+``src/audian/statisticsanalyzer.py``) without Qt, on top of regions that are reduced on the
+device.
+
+The reference cuts every trace to the selected region (``Data.get_region``, data.py:102-118) and hands the cuts to
+every ``Analyzer.analyze(t0, t1, channel, traces)`` (analyzer.py:100; driven by ``DataBrowser.analyze_region``,
+databrowser.py:1759-1775).  Here ``TraceGraph.get_region`` hands out ``Region`` objects instead of arrays: a
+``Region`` looks like ``trace[i0:i1, channel]``, but ``np.mean``, ``np.std``, ``np.min``, ``np.max``,
+``np.argmin`` and ``np.argmax`` of it -- numpy calls the object's own methods for anything that is not an
+ndarray -- are served by ONE ``hipdsp_region_stats`` launch over the trace's device mirror, and 64 bytes come
+back.  Only an analyzer that indexes the region (or asks numpy for anything else) makes it an array, once.
+
+What is left out: thunderlab's ``TableData`` (a plain column / row table stands in for it), the event plot items
+(``make_trace_events`` ... ``add_events``) and the Qt table dialog.
+"""
+
+from math import floor, log10
+
+import numpy as np
+
+
+class Region(object):
+    """Frames [i0, i1) of one channel of a trace, as ``Data.get_region`` cuts them (data.py:112), lazily.
+
+    ``shape``, ``ndim``, ``dtype`` (float64) and ``len()`` touch nothing.  ``mean / std / min / max / argmin /
+    argmax`` with the arguments numpy's free functions pass (``axis=None, dtype=None, out=None, ddof=0``) come from
+    one cached ``trace.region_stats`` call; with any other argument, and for indexing, ``np.asarray`` and every
+    other attribute, the region becomes ``trace[i0:i1, channel]`` (once; ``materialised`` counts it) and numpy
+    does the rest."""
+
+    materialised = 0           # how many regions have become arrays in this process (tests read it)
+
+    def __init__(self, trace, i0, i1, channel):
+        self._trace, self._channel = trace, channel
+        self._i0, self._i1 = int(i0), max(int(i0), int(i1))
+        self._data = None
+        self._slots = None
+
+    @property
+    def shape(self):
+        return (self._i1 - self._i0,) + tuple(self._trace.shape[2:])
+
+    @property
+    def ndim(self):
+        return len(self.shape)
+
+    @property
+    def size(self):
+        return int(np.prod(self.shape, dtype=np.int64))
+
+    dtype = np.dtype(np.float64)
+
+    def __len__(self):
+        return self._i1 - self._i0
+
+    def _materialise(self):
+        if self._data is None:
+            self._data = np.asarray(self._trace[self._i0:self._i1, self._channel], dtype=np.float64)
+            Region.materialised += 1
+        return self._data
+
+    def _stats(self):
+        """The eight slots of BufferedData.region_stats for this region (one launch, cached)."""
+        if self._slots is None:
+            self._trace.update_buffer(self._i0, self._i1)        # what trace[i0:i1] does before it reads
+            self._slots = self._trace.region_stats([(self._i0, self._i1)], self._channel)[0]
+        return self._slots
+
+    def __array__(self, dtype=None, copy=None):
+        return np.asarray(self._materialise(), dtype=dtype)
+
+    def __getitem__(self, key):
+        return self._materialise()[key]
+
+    def __iter__(self):
+        return iter(self._materialise())
+
+    def __getattr__(self, name):
+        if name.startswith('_'):
+            raise AttributeError(name)
+        return getattr(self._materialise(), name)
+
+    def _plain(self, axis, dtype, out, kwargs):
+        """Is this the call of numpy's free function with nothing but its defaults, on a region that has samples?"""
+        rest = {k: v for k, v in kwargs.items()
+                if not ((k == 'keepdims' and v is False) or (k == 'where' and v is True) or (k == 'ddof' and v == 0))}
+        return axis is None and dtype is None and out is None and not rest and self.size > 0
+
+    def mean(self, axis=None, dtype=None, out=None, **kwargs):
+        if self._plain(axis, dtype, out, kwargs):
+            return np.float64(self._stats()[1])
+        return np.mean(self._materialise(), axis=axis, dtype=dtype, out=out, **kwargs)
+
+    def std(self, axis=None, dtype=None, out=None, ddof=0, **kwargs):
+        if self._plain(axis, dtype, out, dict(kwargs, ddof=ddof)):
+            return np.float64(self._stats()[2])
+        return np.std(self._materialise(), axis=axis, dtype=dtype, out=out, ddof=ddof, **kwargs)
+
+    def min(self, axis=None, out=None, **kwargs):
+        if self._plain(axis, None, out, kwargs):
+            return np.float64(self._stats()[3])
+        return np.min(self._materialise(), axis=axis, out=out, **kwargs)
+
+    def max(self, axis=None, out=None, **kwargs):
+        if self._plain(axis, None, out, kwargs):
+            return np.float64(self._stats()[4])
+        return np.max(self._materialise(), axis=axis, out=out, **kwargs)
+
+    def argmin(self, axis=None, out=None, **kwargs):
+        if self._plain(axis, None, out, kwargs):
+            return np.intp(self._stats()[5])
+        return np.argmin(self._materialise(), axis=axis, out=out, **kwargs)
+
+    def argmax(self, axis=None, out=None, **kwargs):
+        if self._plain(axis, None, out, kwargs):
+            return np.intp(self._stats()[6])
+        return np.argmax(self._materialise(), axis=axis, out=out, **kwargs)
+
+
+class Table(object):
+    """Columns with a label, a unit and a format, and rows of values: the part of thunderlab's TableData the
+    analyzers use (``append``, ``add``, ``clear_data``, ``rows``, ``columns``)."""
+
+    def __init__(self):
+        self.labels, self.units, self.formats = [], [], []
+        self.data = []
+
+    def append(self, label, unit=None, formats=None):
+        self.labels.append(label)
+        self.units.append(unit or '')
+        self.formats.append(formats or '%g')
+
+    def add(self, values, column=0):
+        values = list(values)
+        if column != 0 or len(values) != len(self.labels):
+            raise ValueError(f'{len(values)} values for {len(self.labels)} columns')
+        self.data.append(values)
+
+    def clear_data(self):
+        self.data = []
+
+    def rows(self):
+        return len(self.data)
+
+    def columns(self):
+        return len(self.labels)
+
+    def __len__(self):
+        return len(self.data)
+
+    def write_csv(self, path):
+        with open(path, 'w') as f:
+            f.write(','.join(f'{lb}/{u}' if u else lb for lb, u in zip(self.labels, self.units)) + '\n')
+            for row in self.data:
+                f.write(','.join(fm % v if isinstance(v, (int, float, np.number)) else str(v)
+                                 for fm, v in zip(self.formats, row)) + '\n')
+
+
+class Analyzer(object):
+    """Base class for analyzing selected regions (analyzer.py:13-183 without the event markers): implement
+    ``analyze()``; the constructor adds columns with ``make_column()``, ``analyze()`` fills a row with
+    ``store()``.  `graph` is the TraceGraph (the reference passes its DataBrowser); the analyzer registers
+    itself there."""
+
+    def __init__(self, graph, name, source_name):
+        self.graph = graph
+        self.name = name
+        self.source_name = source_name
+        self.source = self.trace(self.source_name)
+        self.data = Table()
+        graph.add_analyzer(self)
+
+    def clear(self):
+        self.data.clear_data()
+
+    def analyze(self, t0, t1, channel, traces):
+        """Called for every analyzed region with ``traces[name] = (time, data)`` -- ``(time, frequencies, data)``
+        for a spectrogram -- of `channel` between `t0` and `t1`; `data` is a Region."""
+        pass
+
+    def analyze_many(self, regions, channels):
+        """The table rows of many regions and channels at once (TraceGraph.analyze_regions): return False to be
+        called region by region through analyze() instead."""
+        return False
+
+    def traces(self):
+        return [t.name for t in self.graph.traces]
+
+    def trace(self, name):
+        return self.graph[name]
+
+    def make_column(self, label, unit=None, formats=None):
+        self.data.append(label, unit, formats)
+
+    def store(self, *args):
+        self.data.add(args, 0)
+
+    def rows(self):
+        """The stored rows, a list of lists in the order of the columns."""
+        return [list(row) for row in self.data.data]
+
+    def save_csv(self, path):
+        """The table as CSV: a header line of ``label/unit``, then the rows in the columns' formats."""
+        self.data.write_csv(path)
+
+
+class PlainAnalyzer(Analyzer):
+    """Stores start, end and duration of the region and the channel (analyzer.py:311-343)."""
+
+    def __init__(self, graph):
+        super().__init__(graph, 'plain', 'data')
+        nd = max(0, int(floor(-log10(1/self.source.rate))))
+        self.make_column('tstart', 's', f'%.{nd}f')
+        self.make_column('tend', 's', f'%.{nd}f')
+        self.make_column('duration', 's', f'%.{nd}f')
+        self.make_column('channel', '', '%.0f')
+
+    def analyze(self, t0, t1, channel, traces):
+        self.store(t0, t1, t1 - t0, channel)
+
+    def analyze_many(self, regions, channels):
+        for t0, t1 in regions:
+            for c in channels:
+                self.store(t0, t1, t1 - t0, c)
+        return True
+
+
+class StatisticsAnalyzer(Analyzer):
+    """Mean and standard deviation of the region of one trace (statisticsanalyzer.py:6-20)."""
+
+    def __init__(self, graph, source_name='filtered'):
+        super().__init__(graph, 'statistics', source_name)
+        nd = max(0, int(-np.floor(np.log10(self.source.ampl_max/4e4))))
+        us = self.source.unit
+        self.make_column(f'{self.source_name} mean', us, f'%.{nd}f')
+        self.make_column(f'{self.source_name} stdev', us, f'%.{nd}f')
+
+    def analyze(self, t0, t1, channel, traces):
+        source = traces[self.source_name][-1]      # the reference's [1]; for a spectrogram that is the frequencies
+        self.store(np.mean(source), np.std(source))
+
+    def analyze_many(self, regions, channels):
+        trace = self.source
+        spans = [self.graph.region_frames(trace, t0, t1) for t0, t1 in regions]
+        if spans:
+            trace.update_buffer(min(a for a, b in spans), max(b for a, b in spans))
+        stats = trace.region_stats(spans)                       # 16 regions per launch
+        for k in range(len(spans)):
+            for c in channels:
+                self.store(stats[k, c, 1], stats[k, c, 2])
+        return True

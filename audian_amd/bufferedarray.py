@@ -19,6 +19,23 @@ It is written from that contract, not from audioio's source.
 import numpy as np
 
 
+def _host_region_stats(block):
+    """The eight slots of hipdsp_region_stats for every channel of a (frames, channels[, F]) float64 block, with
+    numpy itself: (channels, 8)."""
+    channels = block.shape[1]
+    out = np.zeros((channels, 8))
+    out[:, 0] = block.size//max(1, channels)
+    if block.size == 0:
+        out[:, 1:5] = np.nan
+        out[:, 5:7] = -1
+        return out
+    with np.errstate(all='ignore'):
+        for c in range(channels):
+            v = block[:, c].reshape(-1)
+            out[c, 1:7] = np.mean(v), np.std(v), np.min(v), np.max(v), np.argmin(v), np.argmax(v)
+    return out
+
+
 class BufferedArray(object):
 
     def __init__(self, verbose=0):
@@ -187,6 +204,19 @@ class BufferedArray(object):
 
     def update_time(self, start, stop):
         self.update_buffer(int(start*self.rate), int(stop*self.rate) + 1)
+
+    def region_stats(self, regions, channel=None):
+        """n, mean, std, min, max, argmin, argmax, 0 of frames [start, stop) (absolute, inside the current buffer) for
+        every (start, stop) of `regions`, with numpy on the host buffer: (R, channels, 8), or (R, 8) for one channel
+        (BufferedData.region_stats is the same on the device mirror)."""
+        n = len(self._buf())
+        rel = [(int(a) - self.offset, int(b) - self.offset) for a, b in regions]
+        if any(a < 0 or b > n or b < a for a, b in rel):
+            raise IndexError('range outside the loaded buffer')
+        res = np.zeros((len(rel), self.channels, 8))
+        for k, (a, b) in enumerate(rel):
+            res[k] = _host_region_stats(np.asarray(self.buffer[a:b], dtype=np.float64))
+        return res[:, channel] if channel is not None else res
 
     def __getitem__(self, key):
         if not isinstance(key, tuple):

@@ -540,6 +540,32 @@ class BufferedData(BufferedArray):
             res[:, 1::2] = np.maximum.reduceat(buf, seg, axis=0).T
         return res[channel] if channel is not None else res
 
+    def region_stats(self, regions, channel=None):
+        """Statistics of frames [start, stop) for every (start, stop) of `regions` (absolute frame indices inside
+        the current buffer): n, mean, std (ddof 0), min, max, argmin, argmax (first occurrence, relative to the
+        region's first element), 0 -- numpy's np.mean / np.std / np.min / np.max / np.argmin / np.argmax of
+        ``trace[start:stop, channel]`` in float64, which is what the reference's analyzers compute of a selected
+        region (src/audian/statisticsanalyzer.py:18-20), NaN and -1 for an empty region.  A spectrogram's region is
+        its (frames, F) block, positions are flat indices into it.  Runs on the device mirror when it is valid
+        over every region (hipdsp_region_stats, 16 regions per launch; 64 bytes per region and channel come back),
+        else numpy on the host buffer.  Nothing is read back from the mirror: the host copy stays as stale as it
+        was.  Returns (R, channels, 8), or (R, 8) for one channel."""
+        from . import hipdsp
+        n = len(self._hostbuf)
+        rel = [(int(a) - self.offset, int(b) - self.offset) for a, b in regions]
+        if any(a < 0 or b > n or b < a for a, b in rel):
+            raise IndexError('range outside the loaded buffer')
+        if not (rel and self.channels > 0 and self._dev is not None and
+                all(_covers(self._dev_valid, a, b) for a, b in rel)):
+            return BufferedArray.region_stats(self, regions, channel)
+        res = np.zeros((len(rel), self.channels, 8))
+        inner = self._inner()
+        scaled = [(a*inner, b*inner) for a, b in rel]
+        for k in range(0, len(scaled), 16):
+            res[k:k + 16] = hipdsp.region_stats(self.ctx, self._dev, self._pitch(), self.channels, n*inner,
+                                                scaled[k:k + 16])
+        return res[:, channel] if channel is not None else res
+
     # ---- the reference's surface (src/audian/buffereddata.py), restated --------------
     def expand_times(self, tbefore, tafter):
         """Widen this trace's own margins by what a derived trace needs; returns what the source

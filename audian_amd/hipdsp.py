@@ -577,6 +577,25 @@ def fir_bank(ctx, plan, x, x_pitch, channels, frames, first, step, n_out, out, r
                               int(out_kernel_pitch)))
 
 
+def region_stats(ctx, x, x_pitch, channels, frames, regions, out=None):
+    """n, mean, std, min, max, argmin, argmax, 0 of x[c, start:stop] for every (start, stop) of `regions` (element ranges;
+    at most 16) and every channel (hipdsp_region_stats): one pass over the regions on the device.  Returns the
+    (len(regions), channels, 8) float64 host array -- those 64 bytes per region and channel are all that crosses to the
+    host -- or, with `out` (a DeviceArray of that shape), fills it and returns it without any copy."""
+    regions = [(int(a), int(b)) for a, b in regions]
+    start = (ctypes.c_int64*max(1, len(regions)))(*[r[0] for r in regions])
+    stop = (ctypes.c_int64*max(1, len(regions)))(*[r[1] for r in regions])
+    dev = out if out is not None else DeviceArray(ctx, (max(1, len(regions)), max(1, int(channels)), 8), np.float64)
+    _count('region_stats')
+    check(lib.hipdsp_region_stats(ctx.handle, _p(x), int(x_pitch), int(channels), int(frames), start, stop,
+                                  len(regions), _p(dev)))
+    if out is not None:
+        return out
+    res = dev.to_host()[:len(regions), :int(channels)] if int(channels) > 0 else np.zeros((len(regions), 0, 8))
+    dev.free()
+    return res
+
+
 def memcpy2d(ctx, dst, dst_pitch_bytes, src, src_pitch_bytes, width_bytes, height):
     check(lib.hipdsp_memcpy2d_d2d(ctx.handle, _p(dst), int(dst_pitch_bytes), _p(src),
                                   int(src_pitch_bytes), int(width_bytes), int(height)))

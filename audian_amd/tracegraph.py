@@ -2,9 +2,14 @@
 (``src/audian/data.py:121-236`` in /root/reference): put the traces in dependency order, add up
 the pre/post-roll every level needs, open the raw loader and the derived traces, and re-align
 the derived buffers whenever the visible time window moves.  Tests, the streaming demo and
-integrators use it; the Qt application keeps its own ``Data``."""
+integrators use it; the Qt application keeps its own ``Data``.  It also carries the region analysis the reference
+splits between ``Data.get_region`` (data.py:102-118) and ``DataBrowser.analyze_region`` (databrowser.py:1759-1775)."""
 
+import numpy as np
+
+from .analyzer import Region
 from .bufferedarray import ArrayLoader
+from .bufferedspectrogram import BufferedSpectrogram
 
 ROOT = 'data'          # name of the raw recording every chain starts from
 
@@ -19,6 +24,7 @@ class TraceGraph(object):
         self.buffer_time, self.back_time = buffer_time, back_time
         self.data = None
         self.traces, self.sources = [], []
+        self.analyzers = []
         self.tbefore = self.tafter = 0
 
     def add_trace(self, trace):
@@ -94,3 +100,53 @@ class TraceGraph(object):
         for trace in self.traces[1:]:
             if trace.need_update:
                 trace.align_buffer()
+
+    # ---- region analysis ------------------------------------------------------------------
+    def add_analyzer(self, analyzer):
+        self.analyzers.append(analyzer)
+
+    @staticmethod
+    def region_frames(trace, t0, t1):
+        """Frames [i0, i1) of `trace` that Data.get_region cuts for the times [t0, t1] (data.py:105-110)."""
+        i0 = max(int(t0*trace.rate), 0)
+        i1 = min(int(t1*trace.rate) + 1, len(trace))
+        return i0, max(i0, i1)
+
+    def get_region(self, t0, t1, channel):
+        """Every trace cut to [t0, t1] s of one channel, as Data.get_region returns it (data.py:102-118):
+        ``{name: (time, data)}``, ``(time, frequencies, data)`` for a spectrogram.  `data` is a lazy Region: numpy's
+        mean / std / min / max / argmin / argmax of it are reduced on the device, anything else makes it the array
+        ``trace[i0:i1, channel]``."""
+        traces = {}
+        for t in self.traces:
+            i0, i1 = self.region_frames(t, t0, t1)
+            time = np.arange(i0, i1)/t.rate
+            data = Region(t, i0, i1, channel)
+            if isinstance(t, BufferedSpectrogram):
+                traces[t.name] = (time, t.frequencies, data)
+            else:
+                traces[t.name] = (time, data)
+        return traces
+
+    def _clip_times(self, t0, t1):
+        return max(t0, 0), min(t1, self.data.frames/self.data.rate)
+
+    def analyze_region(self, t0, t1, channel):
+        """Hand the region to every analyzer (DataBrowser.analyze_region, databrowser.py:1759-1768)."""
+        t0, t1 = self._clip_times(t0, t1)
+        traces = self.get_region(t0, t1, channel)
+        for a in self.analyzers:
+            a.analyze(t0, t1, channel, traces)
+
+    def analyze_regions(self, regions, channels=None):
+        """Fill the analyzers' tables for many (t0, t1) regions and channels (all of them by default), rows in
+        region-major order.  An analyzer that implements analyze_many() -- StatisticsAnalyzer: one launch per 16
+        regions, all channels at once -- does it in one go; every other one is called region by region."""
+        regions = [self._clip_times(t0, t1) for t0, t1 in regions]
+        channels = list(range(self.data.channels)) if channels is None else list(channels)
+        for a in self.analyzers:
+            if a.analyze_many(regions, channels):
+                continue
+            for t0, t1 in regions:
+                for c in channels:
+                    a.analyze(t0, t1, c, self.get_region(t0, t1, c))

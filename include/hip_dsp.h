@@ -591,6 +591,51 @@ int hipdsp_fir_bank(hipdsp_ctx *ctx, const hipdsp_firplan *plan, const float *x,
                     int64_t channels, int64_t frames, int64_t first, int64_t step, int64_t n_out, int rectify,
                     float *out, int64_t out_pitch, int64_t out_kernel_pitch);
 
+/* ---- region analysis -------------------------------------------------------- */
+
+/* Statistics of selected regions, reduced on the device: what the reference computes after the user selects a region.
+ * DataBrowser.analyze_region (src/audian/databrowser.py:1759-1775) cuts every trace to the region with
+ * Data.get_region(t0, t1, channel) (src/audian/data.py:102-118) and hands the cuts to every
+ * Analyzer.analyze(t0, t1, channel, traces) (src/audian/analyzer.py:100); the analyzer enabled by default,
+ * StatisticsAnalyzer (src/audian/statisticsanalyzer.py:18-20), stores np.mean(source), np.std(source).
+ * x is planar float32: `channels` rows of `frames` valid elements, x_pitch elements apart (0 = frames).  A spectrogram
+ * slab (channels, frames', F) is the same thing with frames = frames' * F: a frame range of one channel is contiguous.
+ * host_start / host_stop are HOST arrays of n_regions element ranges, 0 <= start <= stop <= frames; they travel to the
+ * kernels by value: no upload, no host synchronisation.  out is a DEVICE array (n_regions, channels, 8) float64,
+ * compact.  For region r, channel c and v = x[c, start:stop], out[r][c] holds
+ *   [0] n = stop - start        [1] np.mean(v) (float64)    [2] np.std(v) (ddof 0)      [3] np.min(v)
+ *   [4] np.max(v)               [5] np.argmin(v)            [6] np.argmax(v)            [7] 0 (reserved)
+ * (positions: the first occurrence, relative to start).  Up to 16 regions per call (more: HIPDSP_ERR_UNSUPPORTED).
+ * HIPDSP_ERR_INVALID: n_regions < 1, a NULL list, a range outside [0, frames] or with stop < start, more than 65535
+ * channels.  channels == 0 writes nothing.  Rows and regions start at any 4-byte address; index arithmetic is 64-bit;
+ * at most 2^31 - 1 chunks of 16384 elements per call, all regions together.
+ * Uses the context scratch: 40 bytes per channel and 16384-element chunk, sum over the regions of
+ * ceil((stop - start) / 16384) chunks (at least 40 bytes per channel) -- like hipdsp_mean_spectrum_db it may not come
+ * between phase 1 and phase 2 of hipdsp_sosfilt_envelope.
+ *
+ * Special values (numpy's own results, tested against numpy):
+ *   n == 0                 [1]-[4] NaN, [5] and [6] -1.
+ *   a NaN in the region    [1]-[4] NaN, [5] and [6] the position of the first NaN.
+ *   +-inf and no NaN       [2] NaN; [1] +inf, -inf, or NaN when both signs occur; [3]-[6] by ordinary comparison.
+ * They are carried as flags (saw NaN, saw +inf, saw -inf, first NaN) beside the sums and resolved in the last step;
+ * other channels and other regions are not affected.
+ *
+ * Accuracy contract for finite input.  The sums are pivot-shifted and carried in float64: with K = x[c, start],
+ * d_i = x_i - K, S1 = sum d_i and S2 = sum d_i^2, mean = K + S1/n and std^2 = max(S2/n - (S1/n)^2, 0).  For EVERY
+ * summation order of S1 and S2, with u = 2^-53, g = (n+3)u / (1 - (n+3)u), D1 = mean |d_i|, D2 = mean d_i^2 and mu,
+ * sigma^2 the exact mean and variance of the float32 values,
+ *     |mean - mu|             <= g*D1 + u*|mu|
+ *     |std^2 - sigma^2| = E   <= 3g*D2 + 4u*sigma^2          (|mean d| * D1 <= D1^2 <= D2)
+ *     |std - sigma|           <= min(sqrt(E), E / sigma)
+ * and [0], [3]-[6] are exact.  (float32 accumulation does not satisfy this, nor does an unshifted E[x^2] - mean^2
+ * under a DC offset.)
+ * Determinism: no float atomics; the same call gives the same bits twice.  The chunk grid of a region is anchored at
+ * the region's own start and sized by its length, and the chunks are merged in an order fixed by their count: a
+ * region's eight values do not depend on which other regions ride in the call nor on how many channels it has -- a
+ * 16-region call gives bit for bit what 16 one-region calls give. */
+int hipdsp_region_stats(hipdsp_ctx *ctx, const float *x, int64_t x_pitch, int64_t channels, int64_t frames,
+                        const int64_t *host_start, const int64_t *host_stop, int n_regions, double *out);
+
 /* ---- multi-GPU exchange ---------------------------------------- */
 
 /* One process per GPU, channels sharded in contiguous blocks of the planar layout, so

@@ -152,6 +152,18 @@ for b in builds:
     logs[b['name']].append(f'{"hipdsp_fir_bank, 16 kernels of 257 taps, step 96":78s} {ms:8.3f} ms {nbytes/ms/1e6:7.0f} GB/s')
     if b is builds[-1]:
         print(logs[b['name']][-1], flush=True)
+# ---- hipdsp_region_stats: the whole filtered buffer as one region, every channel (tools/region_stats_bench.py has the short
+# regions and hipdsp_minmax_decimate over the same ranges)
+for b in builds:
+    h, ctx = b['h'], b['ctx']
+    if not hasattr(h.lib, 'hipdsp_region_stats'):
+        continue
+    stats = h.DeviceArray(ctx, (1, C, 8), np.float64)
+    ms = min(timed(b, lambda: h.region_stats(ctx, b['buf']['df'], T, C, T, [(0, T)], out=stats), 5) for _ in range(rounds))
+    ctx.synchronize()
+    logs[b['name']].append(f'{"hipdsp_region_stats, the whole buffer as one region":78s} {ms:8.3f} ms {4.0*S/ms/1e6:7.0f} GB/s')
+    if b is builds[-1]:
+        print(logs[b['name']][-1], flush=True)
 prefix = os.environ.get('OUT_PREFIX')
 if prefix:
     for name, lines in logs.items():
