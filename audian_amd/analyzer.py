@@ -10,8 +10,13 @@ databrowser.py:1759-1775).  Here ``TraceGraph.get_region`` hands out ``Region`` 
 ndarray -- are served by ONE ``hipdsp_region_stats`` launch over the trace's device mirror, and 64 bytes come
 back.  Only an analyzer that indexes the region (or asks numpy for anything else) makes it an array, once.
 
-What is left out: thunderlab's ``TableData`` (a plain column / row table stands in for it), the event plot items
-(``make_trace_events`` ... ``add_events``) and the Qt table dialog.
+The event surface (``make_trace_events``, ``make_panel_events``, ``set_events``, ``add_events``; analyzer.py:186-308)
+is there without Qt: where the reference keeps one ``pyqtgraph.ScatterPlotItem`` per channel, ``events[name][channel]``
+holds the marker coordinates as a plain ``(x, y)`` pair of arrays and ``event_styles[name]`` what the item would have
+been given.  ``TraceGraph.detect_events`` / ``analyze_events`` supply the events of a trace and analyze their regions.
+
+What is left out: thunderlab's ``TableData`` (a plain column / row table stands in for it), the drawing of the event
+markers and the Qt table dialog.
 """
 
 from math import floor, log10
@@ -157,7 +162,7 @@ class Table(object):
 
 
 class Analyzer(object):
-    """Base class for analyzing selected regions (analyzer.py:13-183 without the event markers): implement
+    """Base class for analyzing selected regions (analyzer.py:13-308, the event markers as plain arrays): implement
     ``analyze()``; the constructor adds columns with ``make_column()``, ``analyze()`` fills a row with
     ``store()``.  `graph` is the TraceGraph (the reference passes its DataBrowser); the analyzer registers
     itself there."""
@@ -168,10 +173,16 @@ class Analyzer(object):
         self.source_name = source_name
         self.source = self.trace(self.source_name)
         self.data = Table()
+        self.events = {}
+        self.event_styles = {}
         graph.add_analyzer(self)
 
     def clear(self):
+        """Clear the data table and the markers (analyzer.py:91-97)."""
         self.data.clear_data()
+        for name in self.events:
+            for c in range(len(self.events[name])):
+                self.events[name][c] = self._no_events()
 
     def analyze(self, t0, t1, channel, traces):
         """Called for every analyzed region with ``traces[name] = (time, data)`` -- ``(time, frequencies, data)``
@@ -194,6 +205,39 @@ class Analyzer(object):
 
     def store(self, *args):
         self.data.add(args, 0)
+
+    # ---- event markers (analyzer.py:186-308) without plot items ------------------------
+    @staticmethod
+    def _no_events():
+        return np.zeros(0), np.zeros(0)
+
+    def _make_events(self, name, style):
+        self.events[name] = [self._no_events() for c in range(self.graph.data.channels)]
+        self.event_styles[name] = style
+
+    def make_trace_events(self, name, trace_name, symbol, color, size):
+        """Prepare events `name` for marking on top of a trace: one (x, y) pair of arrays per channel."""
+        self._make_events(name, dict(trace=trace_name, panel=None, symbol=symbol, color=color, size=size))
+
+    def make_panel_events(self, name, panel_name, symbol, color, size):
+        """Prepare events `name` for marking in a panel: one (x, y) pair of arrays per channel."""
+        self._make_events(name, dict(trace=None, panel=panel_name, symbol=symbol, color=color, size=size))
+
+    def set_events(self, name, channel, x, y):
+        """Set the markers of `channel` (all channels if negative); those of the other channels are erased."""
+        for c in range(len(self.events[name])):
+            if c == channel or channel < 0:
+                self.events[name][c] = (np.array(x, dtype=np.float64).reshape(-1), np.array(y, dtype=np.float64).reshape(-1))
+            else:
+                self.events[name][c] = self._no_events()
+
+    def add_events(self, name, channel, x, y):
+        """Add markers to `channel` (all channels if negative); nothing is erased."""
+        for c in range(len(self.events[name])):
+            if c == channel or channel < 0:
+                ox, oy = self.events[name][c]
+                self.events[name][c] = (np.concatenate((ox, np.asarray(x, dtype=np.float64).reshape(-1))),
+                                        np.concatenate((oy, np.asarray(y, dtype=np.float64).reshape(-1))))
 
     def rows(self):
         """The stored rows, a list of lists in the order of the columns."""

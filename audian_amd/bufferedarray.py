@@ -218,6 +218,44 @@ class BufferedArray(object):
             res[k] = _host_region_stats(np.asarray(self.buffer[a:b], dtype=np.float64))
         return res[:, channel] if channel is not None else res
 
+    def _event_arguments(self, thresholds, min_gap, min_duration, start, stop):
+        """(per-channel float64 thresholds, min_gap frames, min_len frames, first, last relative to the buffer)."""
+        if len(self.shape) > 2:
+            raise TypeError('detect_events is for traces, not for spectrogram-shaped data')
+        n = len(self._buf())
+        a = 0 if start is None else int(start) - self.offset
+        b = n if stop is None else int(stop) - self.offset
+        if a < 0 or b > n or b < a:
+            raise IndexError('range outside the loaded buffer')
+        thr = np.asarray(thresholds, dtype=np.float64)
+        if thr.ndim > 0 and thr.shape != (self.channels,):
+            raise ValueError('thresholds: one value or one per channel')
+        if min_gap < 0 or min_duration < 0:
+            raise ValueError('negative min_gap or min_duration')
+        # seconds to frames as songdetector.py:137-139 does it
+        return np.broadcast_to(thr, (self.channels,)), int(min_gap*self.rate), int(min_duration*self.rate), a, b
+
+    def detect_events(self, thresholds, min_gap=0.0, min_duration=0.0, start=None, stop=None):
+        """Threshold events of frames [start, stop) (absolute, inside the current buffer; the whole buffer by default)
+        of every channel, with numpy on the host buffer: runs of samples above the channel's threshold (float32
+        comparison, as on the device mirror), runs less than or exactly `min_gap` seconds apart merged, events shorter
+        than `min_duration` seconds dropped (events.py; BufferedData.detect_events is the same on the device mirror).
+        Returns an Events object of absolute frame indices."""
+        from .events import Events, host_detect_events
+        thr, gap, length, a, b = self._event_arguments(thresholds, min_gap, min_duration, start, stop)
+        buf = self.buffer
+        pairs = [host_detect_events(buf[a:b, c], thr[c], gap, length, first=self.offset + a)
+                 for c in range(self.channels)]
+        return Events(pairs, self.rate, getattr(self, 'name', None))
+
+    def event_thresholds(self, factor, start=None, stop=None):
+        """The usual threshold of a detector, mean + factor*std of frames [start, stop) per channel (the alternative
+        songdetector.py:119-127 leaves commented out), from ONE region_stats call over the range."""
+        a = self.offset if start is None else int(start)
+        b = self.offset + len(self._buf()) if stop is None else int(stop)
+        stats = self.region_stats([(a, b)])[0]
+        return stats[:, 1] + float(factor)*stats[:, 2]
+
     def __getitem__(self, key):
         if not isinstance(key, tuple):
             key = (key,)

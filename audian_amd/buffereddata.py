@@ -566,6 +566,24 @@ class BufferedData(BufferedArray):
                                                 scaled[k:k + 16])
         return res[:, channel] if channel is not None else res
 
+    def detect_events(self, thresholds, min_gap=0.0, min_duration=0.0, start=None, stop=None):
+        """Threshold events of frames [start, stop) (absolute frame indices inside the current buffer; by default the
+        whole buffer) of every channel: samples above the channel's threshold (`thresholds`: one value, or one per
+        channel), runs at most int(min_gap*rate) frames apart merged, events shorter than int(min_duration*rate)
+        frames dropped -- what songdetector.py's detect_songs does with an envelope (songdetector.py:113-139; the
+        definition: hipdsp_detect_events in include/hip_dsp.h).  Runs on the device mirror when it is valid over the
+        range (only the counts and the index pairs come back), else numpy on the host buffer.  Nothing is read back
+        from the mirror: the host copy stays as stale as it was.  TypeError for spectrogram-shaped traces.  Returns
+        an Events object of absolute frame indices."""
+        from . import hipdsp
+        from .events import Events
+        thr, gap, length, a, b = self._event_arguments(thresholds, min_gap, min_duration, start, stop)
+        if not (self.channels > 0 and b > a and self._dev is not None and _covers(self._dev_valid, a, b)):
+            return BufferedArray.detect_events(self, thresholds, min_gap, min_duration, start, stop)
+        pairs = hipdsp.detect_events(self.ctx, self._dev, self._pitch(), self.channels, a, b,
+                                     thr if np.ndim(thresholds) > 0 else float(thr[0]), gap, length)
+        return Events([p + self.offset for p in pairs], self.rate, self.name)
+
     # ---- the reference's surface (src/audian/buffereddata.py), restated --------------
     def expand_times(self, tbefore, tafter):
         """Widen this trace's own margins by what a derived trace needs; returns what the source

@@ -596,6 +596,60 @@ def region_stats(ctx, x, x_pitch, channels, frames, regions, out=None):
     return res
 
 
+def detect_events_into(ctx, x, x_pitch, channels, start, stop, thresholds, min_gap, min_len, capacity, events, counts,
+                       events_pitch=0):
+    """One hipdsp_detect_events launch, everything staying on the device: `events` (channels, capacity, 2) int64 (None with
+    capacity 0) and `counts` (channels,) int64 are DeviceArrays; `thresholds` is a number for all channels or a
+    DeviceArray of `channels` float32."""
+    per_channel = isinstance(thresholds, DeviceArray) or hasattr(thresholds, 'data_ptr')
+    _count('detect_events')
+    check(lib.hipdsp_detect_events(ctx.handle, _p(x), int(x_pitch), int(channels), int(start), int(stop),
+                                   _p(thresholds if per_channel else None), 0.0 if per_channel else float(thresholds),
+                                   int(min_gap), int(min_len), int(capacity), _p(events), int(events_pitch), _p(counts)))
+
+
+def detect_events(ctx, x, x_pitch, channels, start, stop, thresholds, min_gap, min_len, capacity=None):
+    """Threshold events of x[c, start:stop] (hipdsp_detect_events): runs of samples > threshold, runs at most `min_gap`
+    samples apart merged, merged events shorter than `min_len` dropped.  `thresholds` is one number or one per channel.
+    Returns a list of `channels` (K, 2) int64 arrays of (onset, offset) row positions, ascending.  With capacity=None
+    the call starts with room for 4096 events per channel and is repeated once, with the largest count, if a channel
+    has more; with a number, at most that many events per channel come back.  Only the counts and the written pairs
+    cross to the host."""
+    channels = int(channels)
+    if channels <= 0:
+        return []
+    thr = np.asarray(thresholds, dtype=np.float64)
+    dthr = None
+    if thr.ndim > 0:
+        if thr.shape != (channels,):
+            raise ValueError('thresholds: one value or one per channel')
+        dthr = DeviceArray.from_host(ctx, thr.astype(np.float32))
+    cap = 4096 if capacity is None else int(capacity)
+    dcounts = DeviceArray(ctx, (channels,), np.int64)
+    try:
+        while True:
+            dev = DeviceArray(ctx, (channels, cap, 2), np.int64) if cap > 0 else None
+            detect_events_into(ctx, x, x_pitch, channels, start, stop, dthr if dthr is not None else float(thr), min_gap,
+                               min_len, cap, dev, dcounts)
+            counts = dcounts.to_host()
+            most = int(counts.max())
+            if capacity is None and most > cap:
+                dev.free()
+                cap = most
+                continue
+            out = []
+            for c in range(channels):
+                k = min(int(counts[c]), cap)
+                out.append(dev.view(c*cap*2, (k, 2)).to_host() if k > 0 else np.zeros((0, 2), dtype=np.int64))
+            if dev is not None:
+                dev.free()
+            return out
+    finally:
+        dcounts.free()
+        if dthr is not None:
+            dthr.free()
+
+
 def memcpy2d(ctx, dst, dst_pitch_bytes, src, src_pitch_bytes, width_bytes, height):
     check(lib.hipdsp_memcpy2d_d2d(ctx.handle, _p(dst), int(dst_pitch_bytes), _p(src),
                                   int(src_pitch_bytes), int(width_bytes), int(height)))

@@ -3,7 +3,8 @@
 the pre/post-roll every level needs, open the raw loader and the derived traces, and re-align
 the derived buffers whenever the visible time window moves.  Tests, the streaming demo and
 integrators use it; the Qt application keeps its own ``Data``.  It also carries the region analysis the reference
-splits between ``Data.get_region`` (data.py:102-118) and ``DataBrowser.analyze_region`` (databrowser.py:1759-1775)."""
+splits between ``Data.get_region`` (data.py:102-118) and ``DataBrowser.analyze_region`` (databrowser.py:1759-1775), and
+the event detection that the reference's ``songdetector.py`` puts in front of it (detect_songs, songdetector.py:113-139)."""
 
 import numpy as np
 
@@ -150,3 +151,43 @@ class TraceGraph(object):
             for t0, t1 in regions:
                 for c in channels:
                     a.analyze(t0, t1, c, self.get_region(t0, t1, c))
+
+    # ---- event detection ---------------------------------------------------------------------
+    def _event_frames(self, trace, t0, t1):
+        """The frames of `trace` for the times [t0, t1] (None: the buffer as it is), with the buffers moved there as for
+        a visible window (update_times)."""
+        if t0 is None and t1 is None:
+            return None, None
+        t0 = 0.0 if t0 is None else t0
+        t1 = len(trace)/trace.rate if t1 is None else t1
+        self.update_times(t0, t1)               # the raw buffer, then the derived traces that are needed
+        i0, i1 = self.region_frames(trace, t0, t1)
+        if trace is self.data:
+            trace.update_buffer(i0, i1)         # (a raw loader that is not shown does not follow update_times)
+        return i0, i1
+
+    def event_thresholds(self, trace_name, factor, t0=None, t1=None):
+        """mean + factor*std of the trace between t0 and t1 (by default its current buffer), one value per channel:
+        the usual threshold of a detector (songdetector.py:119-127), from one region_stats call."""
+        trace = self[trace_name]
+        i0, i1 = self._event_frames(trace, t0, t1)
+        return trace.event_thresholds(factor, i0, i1)
+
+    def detect_events(self, trace_name, thresholds, min_gap=0.0, min_duration=0.0, t0=None, t1=None):
+        """Threshold events of a trace between t0 and t1 seconds (by default its current buffer): the buffer is moved
+        to cover the range, then the trace detects (BufferedData.detect_events: on its device mirror when it has
+        one).  The buffers move as for a visible window (update_times), so the graph's buffer_time has to hold the
+        range as it has to hold a window; a range that is not resident afterwards is an IndexError.  Returns an Events
+        object."""
+        trace = self[trace_name]
+        i0, i1 = self._event_frames(trace, t0, t1)
+        return trace.detect_events(thresholds, min_gap, min_duration, i0, i1)
+
+    def analyze_events(self, events, channels=None):
+        """Fill the analyzers' tables with the regions of the events, channel by channel: every event is analyzed on
+        its own channel only, so StatisticsAnalyzer gets one row per event (songdetector.py:141-143 analyzes each
+        detected song's region the same way)."""
+        for c in (range(events.channels) if channels is None else channels):
+            regions = events.regions(c)
+            if regions:
+                self.analyze_regions(regions, channels=[c])

@@ -636,6 +636,45 @@ int hipdsp_fir_bank(hipdsp_ctx *ctx, const hipdsp_firplan *plan, const float *x,
 int hipdsp_region_stats(hipdsp_ctx *ctx, const float *x, int64_t x_pitch, int64_t channels, int64_t frames,
                         const int64_t *host_start, const int64_t *host_stop, int n_regions, double *out);
 
+/* ---- event detection -------------------------------------------------------- */
+
+/* Threshold events of a device-resident trace: the step between an envelope (or band-power, or kernel-filter) trace
+ * and the analysis of its events' regions, the reference's open item "Add events ... / Provide interface for event
+ * detectors" (README.md:66-69) as its songdetector.py does it (detect_songs, songdetector.py:113-139: threshold
+ * crossings, merge_events, remove_events).  x is planar float32, `channels` rows x_pitch elements apart (x_pitch >=
+ * stop, unless there is one channel); of every row the elements [start, stop) are looked at, 0 <= start <= stop.
+ * The threshold of channel c is dev_thresholds[c] (a DEVICE array of `channels` floats) or, with dev_thresholds ==
+ * NULL, (float)threshold for all.  min_gap >= 0 and min_len >= 0 are counts of elements.  Per row:
+ *   1. above[i] = x[i] > thr, as a float32 comparison: NaN is not above, +inf is above any finite thr, a sample equal
+ *      to thr is not above (and nothing is above a NaN or +inf threshold).
+ *   2. A raw event is a maximal run of above samples, half-open [onset, offset).  A run that touches start or stop is
+ *      reported with onset == start or offset == stop; it is not dropped -- the indices show that it is cut off.
+ *   3. Two consecutive raw events are merged when next.onset - prev.offset <= min_gap, the left side being the number
+ *      of not-above samples between them.  With min_gap == 0 nothing merges.
+ *   4. After merging, an event is kept when offset - onset >= min_len.
+ *   5. The events of a row come out in ascending order; indices are positions in the row, not relative to start.
+ * thunderlab, whose merge_events / remove_events songdetector.py calls, is neither in the reference tree nor in this
+ * image: steps 3 and 4 restate songdetector.py's use of them, parity with thunderlab is unpinned.  The contract is the
+ * definition above; every output is an integer and tests/events_definition.py reproduces it exactly.
+ * Output: counts is a DEVICE array of `channels` int64 and receives the number of events of every row, also when that
+ * exceeds capacity.  events is a DEVICE array (channels, capacity, 2) int64 of (onset, offset) pairs, events_pitch
+ * elements between channels (0 = 2*capacity); only the first min(count, capacity) pairs of a channel are written,
+ * nothing beyond them is touched.  capacity == 0 with events == NULL is legal and gives the counts only.  stop ==
+ * start gives zero counts and writes nothing else; channels == 0 writes nothing.
+ * HIPDSP_ERR_INVALID: a NULL ctx, counts or (with capacity > 0) events, negative sizes, start > stop, x_pitch < stop
+ * with more than one channel, events_pitch < 2*capacity, misaligned pointers.  HIPDSP_ERR_UNSUPPORTED: more than 65535
+ * channels or stop - start > 2^40 elements per call.  Index arithmetic is 64-bit; rows start at any 4-byte address.
+ * No host synchronisation, nothing is read back, legal inside hipdsp_graph_begin/end once the scratch is reserved.
+ * Uses the context scratch: 552 bytes per channel and 4096-element chunk of [start, stop) (the above bits, 1 bit per
+ * sample, and five 8-byte carries per chunk) -- like hipdsp_region_stats it may not come between phase 1 and phase 2
+ * of hipdsp_sosfilt_envelope.  The trace is read once: about 4.4 bytes per sample move in all.
+ * Determinism: the slot of every event comes from prefix scans over the chunks and its rank inside its chunk; there is
+ * no atomic.  The same call gives the same bytes twice, and a channel's result does not depend on which other channels
+ * ride in the call. */
+int hipdsp_detect_events(hipdsp_ctx *ctx, const float *x, int64_t x_pitch, int64_t channels, int64_t start,
+                         int64_t stop, const float *dev_thresholds, double threshold, int64_t min_gap,
+                         int64_t min_len, int64_t capacity, int64_t *events, int64_t events_pitch, int64_t *counts);
+
 /* ---- multi-GPU exchange ---------------------------------------- */
 
 /* One process per GPU, channels sharded in contiguous blocks of the planar layout, so

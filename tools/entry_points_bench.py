@@ -164,6 +164,18 @@ for b in builds:
     logs[b['name']].append(f'{"hipdsp_region_stats, the whole buffer as one region":78s} {ms:8.3f} ms {4.0*S/ms/1e6:7.0f} GB/s')
     if b is builds[-1]:
         print(logs[b['name']][-1], flush=True)
+# ---- hipdsp_detect_events: the envelope of the whole buffer against one threshold, gaps up to 0.1 s merged (tools/events_bench.py
+# has the other gaps and hipdsp_region_stats over the same slab)
+for b in builds:
+    h, ctx = b['h'], b['ctx']
+    if not hasattr(h.lib, 'hipdsp_detect_events'):
+        continue
+    ev, cnt = h.DeviceArray(ctx, (C, 65536, 2), np.int64), h.DeviceArray(ctx, (C,), np.int64)
+    ms = min(timed(b, lambda: h.detect_events_into(ctx, b['buf']['de'], T, C, 0, T, 0.25, 9600, 960, 65536, ev, cnt), 5) for _ in range(rounds))
+    ctx.synchronize()
+    logs[b['name']].append(f'{"hipdsp_detect_events, the whole envelope, min_gap 0.1 s, min_len 0.01 s":78s} {ms:8.3f} ms {4.0*S/ms/1e6:7.0f} GB/s')
+    if b is builds[-1]:
+        print(logs[b['name']][-1], flush=True)
 prefix = os.environ.get('OUT_PREFIX')
 if prefix:
     for name, lines in logs.items():
