@@ -1,24 +1,35 @@
-// sos_plan.hip -- host-side mathematics of the block-parallel biquad cascade (float64, no device code): the plan
+// sos_plan.hip -- host-side mathematics of the block-parallel biquad cascade (no device code): the plan
 // block of an SOS table (transition powers, phase-1 weights, sosfilt_zi, warm-up and pad lengths) and the segment
 // planner.  Reference semantics: scipy.signal.sosfilt / sosfilt_zi / sosfiltfilt as audian calls them
 // (src/audian/bufferedfilter.py:36, src/audian/bufferedenvelope.py:39).
 #include "sos_plan.h"
+#include <cfloat>
 #include <cmath>
 #include <vector>
 
 namespace {
 
-// ---- host-side plan mathematics (float64) -----------------------------------
+// ---- host-side plan mathematics ----------------------------------------------
+// The tables the kernels read (G, M, AT) are float64; they are COMPUTED in the host's extended precision and rounded
+// once.  A cascade with poles next to z = 1 (a 20 Hz low-pass or a 5 Hz band-pass edge at 96 kHz) has a nearly
+// defective transition matrix: the entries of A^n grow like n while the states they are applied to cancel to O(1), and
+// the rounding of ten squarings in float64 came out at 1e-10 of the loudest passage in a tile's start states -- 100
+// float32 roundings of a quiet stretch 80 dB under it (tests/test_gpu_iir_accuracy.py; tests/iir_bound.py has the bound).
+// With tables that are correctly rounded the kernels' own float64 arithmetic stays within that bound.
+typedef long double real;
+#if !defined(__HIP_DEVICE_COMPILE__)
+static_assert(LDBL_MANT_DIG >= 64, "the plan tables need a long double wider than float64 on the host");
+#endif
 
 struct Mat {
     int d;
-    double v[MAXD][MAXD];
+    real v[MAXD][MAXD];
 };
 
 Mat mat_identity(int d)
 {
     Mat m; m.d = d;
-    for (int i = 0; i < MAXD; i++) for (int j = 0; j < MAXD; j++) m.v[i][j] = (i == j && i < d) ? 1.0 : 0.0;
+    for (int i = 0; i < MAXD; i++) for (int j = 0; j < MAXD; j++) m.v[i][j] = (i == j && i < d) ? 1.0L : 0.0L;
     return m;
 }
 
@@ -27,7 +38,7 @@ Mat mat_mul(const Mat &a, const Mat &b)
     Mat m = mat_identity(a.d);
     for (int i = 0; i < a.d; i++)
         for (int j = 0; j < a.d; j++) {
-            double s = 0.0;
+            real s = 0.0L;
             for (int k = 0; k < a.d; k++) s += a.v[i][k] * b.v[k][j];
             m.v[i][j] = s;
         }
@@ -39,18 +50,18 @@ double mat_norm_inf(const Mat &a)
     double n = 0.0;
     for (int i = 0; i < a.d; i++) {
         double s = 0.0;
-        for (int j = 0; j < a.d; j++) s += fabs(a.v[i][j]);
+        for (int j = 0; j < a.d; j++) s += (double)fabsl(a.v[i][j]);
         if (!(s <= n)) n = s;      // NaN propagates as "large"
     }
     return n;
 }
 
 // One time step of the cascade (same arithmetic order as the kernel / scipy).
-void cascade_step(const double coef[MAXS][5], int S, double *z, double x)
+void cascade_step(const double coef[MAXS][5], int S, real *z, real x)
 {
-    double cur = x;
+    real cur = x;
     for (int s = 0; s < S; s++) {
-        double y = coef[s][0] * cur + z[2 * s];
+        real y = coef[s][0] * cur + z[2 * s];
         z[2 * s] = coef[s][1] * cur - coef[s][3] * y + z[2 * s + 1];
         z[2 * s + 1] = coef[s][2] * cur - coef[s][4] * y;
         cur = y;
@@ -81,25 +92,25 @@ int fill_plan(SosPlanDev *p, const double *sos, int S)
         if (!(p->coef[s][0] == 1.0 && p->coef[s][2] == 1.0 && fabs(p->coef[s][1]) == 2.0)) p->unit_tail = 0;
     // state-space (A, B): columns of A from unit states with zero input, B from unit input
     Mat A = mat_identity(D);
-    double B[MAXD] = {0};
+    real B[MAXD] = {0};
     for (int c = 0; c < D; c++) {
-        double z[MAXD] = {0};
-        z[c] = 1.0;
-        cascade_step(p->coef, S, z, 0.0);
+        real z[MAXD] = {0};
+        z[c] = 1.0L;
+        cascade_step(p->coef, S, z, 0.0L);
         for (int r = 0; r < D; r++) A.v[r][c] = z[r];
     }
     {
-        double z[MAXD] = {0};
-        cascade_step(p->coef, S, z, 1.0);
+        real z[MAXD] = {0};
+        cascade_step(p->coef, S, z, 1.0L);
         for (int r = 0; r < D; r++) B[r] = z[r];
     }
     // G[j] = A^(L-1-j) B
     {
-        double g[MAXD];
+        real g[MAXD];
         for (int r = 0; r < D; r++) g[r] = B[r];
         for (int j = L - 1; j >= 0; j--) {
-            for (int r = 0; r < D; r++) p->G[j * D + r] = g[r];
-            double t[MAXD] = {0};
+            for (int r = 0; r < D; r++) p->G[j * D + r] = (double)g[r];
+            real t[MAXD] = {0};
             for (int r = 0; r < D; r++)
                 for (int c = 0; c < D; c++) t[r] += A.v[r][c] * g[c];
             for (int r = 0; r < D; r++) g[r] = t[r];
@@ -111,11 +122,11 @@ int fill_plan(SosPlanDev *p, const double *sos, int S)
     static_assert(L == 32, "plan assumes L == 32");
     for (int k = 0; k < 6; k++) {
         for (int r = 0; r < D; r++)
-            for (int c = 0; c < D; c++) p->M[k * D * D + r * D + c] = pw.v[r][c];
+            for (int c = 0; c < D; c++) p->M[k * D * D + r * D + c] = (double)pw.v[r][c];
         pw = mat_mul(pw, pw);
     }
     for (int r = 0; r < D; r++)
-        for (int c = 0; c < D; c++) p->AT[r * D + c] = pw.v[r][c];
+        for (int c = 0; c < D; c++) p->AT[r * D + c] = (double)pw.v[r][c];
     // pw == A^(L*64) == A^TILE.  warm = TILE * (smallest m with ||A^(TILE*m)|| < 2^-60)
     const double tol = ldexp(1.0, -60);
     const int MAXBITS = 40;

@@ -1,0 +1,191 @@
+"""Calibration of the local IIR bound (tests/iir_bound.py) on the CPU, before any kernel is held to it.
+
+1. The restatement of sosfilt / sosfiltfilt / sosfilt_zi / the pad length agrees in float64 with the C oracle to
+   1e-10 of the channel's peak, the figure test_oracle_golden.py holds the oracle to.
+2. Every (filter, family) pair the GPU tests use meets q <= 2^-6 (a cap on the case list, not a measurement), and
+   its reference stays in float32's normal range.
+3. The correct model -- the sequential float64 run rounded once to float32 -- meets the bound with the factor 16
+   replaced by 1; so does the same run with the odd extensions formed in float32 as the kernels form them, for every
+   low-pass envelope.  An envelope with a high-pass does NOT (the rounding of the extension shows against an answer
+   far under the rectified trace's level): it meets the bound with iir_bound.extension_term, again with 1 for 16.
+   A sweep that hands its forward pass to the backward pass through a float32 tile does not either; it meets the
+   bound with iir_bound.between_term.
+4. Two wrong versions violate the bound: the cascade's state rounded to float32 at every tile border -- while still
+   passing rel_err < 1e-4 on the same data, the gap this bound closes -- and eight-tile segments warmed up over one
+   tile only, on the filter with the longest memory.
+"""
+
+import numpy as np
+import pytest
+
+from conftest import rel_err
+import iir_bound as ib
+
+
+def peak_err(a, b):
+    return max(rel_err(np.asarray(a, dtype=np.float64)[:, c], b[:, c]) for c in range(b.shape[1]))
+
+
+@pytest.mark.parametrize('case', ['lp1 4000 Hz @ 48 kHz', 'hp3 100 Hz @ 192 kHz', 'bp4 300-3000 Hz @ 48 kHz'])
+def test_sosfilt_restatement_is_the_oracles(oracle, case):
+    sos, rate, fams = ib.design(case)
+    x = ib.families(fams, 4096, rate)
+    assert peak_err(ib.sosfilt(sos, x, np.float64), oracle.sosfilt(sos, x.astype(np.float64))) <= 1e-10
+    assert peak_err(ib.sosfilt(sos, x, ib.LD), oracle.sosfilt(sos, x.astype(np.float64))) <= 1e-10
+
+
+@pytest.mark.parametrize('case', list(ib.ENVELOPES))
+def test_sosfiltfilt_restatement_is_the_oracles(oracle, case):
+    sos, rate, fams = ib.design(case, ib.ENVELOPES)
+    assert ib.padlen(sos) == oracle.sosfiltfilt_edge(sos)
+    zi = oracle.sosfilt_zi(sos)
+    assert np.max(np.abs(ib.sosfilt_zi(sos, np.float64) - zi)) <= 1e-10*np.max(np.abs(zi))
+    x = ib.families(fams, 4096, rate)
+    want = oracle.sosfiltfilt(sos, (np.pi/2)*np.abs(x.astype(np.float64)))
+    assert peak_err(ib.sosfiltfilt(sos, x, np.float64, clamp=False), want) <= 1e-10
+    want[want < 0] = 0
+    assert peak_err(ib.sosfiltfilt(sos, x, np.float64), want) <= 1e-10
+    assert np.array_equal(ib.sosfiltfilt(sos, x, np.float64), ib.clamped(ib.sosfiltfilt(sos, x, np.float64, clamp=False)))
+    plain = oracle.sosfiltfilt(sos, x.astype(np.float64))                   # rectify 0: the trace itself, no gain
+    assert peak_err(ib.sosfiltfilt(sos, x, np.float64, gain=1.0, rectify=False, clamp=False), plain) <= 1e-10
+
+
+def test_pad_length_with_first_order_sections(oracle):
+    for case in ib.BANDPASSES:
+        sos = ib.design(case)[0]
+        assert ib.padlen(sos) == oracle.sosfiltfilt_edge(sos), case
+
+
+def test_windows_sit_on_the_grid_of_the_calls_first_sample():
+    ref = np.ones((200, 1))
+    got = ref.copy()
+    got[70, 0] += 3*ib.ULP                                    # sample 75 of the call: window 1
+    rho = ib.ratios(got, ref, first=5)
+    assert rho.shape == (4, 1) and rho[1, 0] == pytest.approx(3.0) and np.all(np.delete(rho[:, 0], 1) == 0)
+    zero = np.zeros((130, 1))
+    assert ib.assert_within(zero, zero, 0.0, 'zeros') == 0.0
+    with pytest.raises(AssertionError):
+        ib.assert_within(zero + 1e-40, zero, 0.0, 'not exactly zero')
+    with pytest.raises(AssertionError):
+        ib.assert_within(np.full((130, 1), np.nan), ref[:130], 0.0, 'NaN')
+
+
+def check_case(ref, run, what):
+    """q under the cap, the reference in range, the rounded float64 run inside the bound with 1 for 16."""
+    q = ib.allowance(run, ref)
+    print('%s: q %s' % (what, ' '.join('%.2g' % v for v in q)))
+    assert np.all(q <= ib.Q_CAP), (what, q)
+    ib.assert_in_range(ref, what)
+    ib.assert_within(run.astype(np.float32), ref, q, what + ', float64 rounded once', margin=1.0)
+    return q
+
+
+@pytest.mark.parametrize('case', list(ib.BANDPASSES) + ['general'])
+def test_bandpass_cases(case):
+    sos, rate, fams = ib.design(ib.GENERAL if case == 'general' else case)
+    if case == 'general':
+        sos = ib.spread(sos)
+    for T in (ib.T_LONG, ib.T_SKIP) if case in ib.SKIP_BANDPASSES else (ib.T_LONG,):
+        x = ib.families(fams, T, rate)
+        ref, run = ib.sosfilt_runs(sos, x)
+        check_case(ref, run, '%s, T %d' % (case, T))
+        if 'onset' in fams:
+            assert np.all(ref[:ib.ONSET, fams.index('onset')] == 0)
+
+
+@pytest.mark.parametrize('case', list(ib.ENVELOPES))
+def test_envelope_cases(case):
+    sos, rate, fams = ib.design(case, ib.ENVELOPES)
+    hp = ib.has_highpass(sos)
+    assert hp == (fams is ib.HP_FAMILIES)
+    for T in (ib.T_LONG, ib.T_SKIP) if case in ib.SKIP_ENVELOPES else (ib.T_LONG,):
+        x = ib.families(fams, T, rate)
+        what = '%s, T %d' % (case, T)
+        ref, run = ib.envelope_runs(sos, x)
+        q = check_case(ref, run, what)
+        model = ib.sosfiltfilt(sos, x, np.float64, clamp=False, right_ext_f32=True).astype(np.float32)
+        if hp:
+            with pytest.raises(AssertionError):
+                ib.assert_within(model, ref, q, what)                       # the whole bound, 16 and all
+            ib.assert_within(model, ref, q, what + ', float32 right extension', margin=1.0, term=ib.extension_term(sos, x))
+        else:
+            worst = ib.assert_within(model, ref, q, what + ', float32 right extension', margin=1.0)
+            print('%s: float32 right extension %.3f' % (what, worst))
+    if case == ib.PLAYBACK:
+        x = ib.families(fams, ib.T_LONG, rate)
+        ref, run = ib.envelope_runs(sos, x, rectify=False)
+        q = check_case(ref, run, case + ', rectify 0')
+        model = ib.sosfiltfilt(sos, x, np.float64, gain=1.0, rectify=False, clamp=False, right_ext_f32=True)
+        ib.assert_within(model.astype(np.float32), ref, q, case + ', rectify 0, float32 right extension', margin=1.0)
+
+
+@pytest.mark.parametrize('case', ['lp8 60 Hz @ 48 kHz', 'bp3 20-300 Hz @ 48 kHz', 'lp4 300 Hz @ 48 kHz'])
+def test_a_float32_tile_between_the_passes_needs_its_term(case):
+    """The sweeps that hand the forward pass to the backward pass through the float32 tile (three- and four-section
+    plans, the frame-split backward sweep): that model misses the bound as it stands and meets it, with 1 for 16, with
+    between_term (and extension_term where the envelope has a high-pass)."""
+    sos, rate, fams = ib.design(case, ib.ENVELOPES)
+    x = ib.families(fams, ib.T_LONG, rate)
+    ref, run = ib.envelope_runs(sos, x)
+    q = ib.allowance(run, ref)
+    model = ib.sosfiltfilt(sos, x, np.float64, clamp=False, right_ext_f32=True, between_f32=True).astype(np.float32)
+    with pytest.raises(AssertionError):
+        ib.assert_within(model, ref, q, case)
+    term = ib.between_term(sos, x)
+    if ib.has_highpass(sos):
+        term = term + ib.extension_term(sos, x)
+    worst = ib.assert_within(model, ref, q, case + ', float32 between the passes', margin=1.0, term=term)
+    plain = np.max(ib.ratios(model, ref))
+    print('%s: float32 between the passes %.3f roundings, %.3f beyond the term' % (case, plain, worst))
+
+
+PAIRS = sorted(set(ib.SOSFILT_ENVELOPE) | set(ib.CHAIN.values()) | set(ib.SPLIT_FRAMES))
+
+
+@pytest.mark.parametrize('bp,env', PAIRS)
+def test_fused_pairs(bp, env):
+    """The envelope of a band-pass output rounded to float32 (the float64 run stands in for the launch's own), from
+    sample 0 and from ENV_FIRST[1], where the kernels form the left extension in float32 too."""
+    sos, rate, fams = ib.design(bp)
+    esos, _, efams = ib.design(env, ib.ENVELOPES)
+    hp = ib.has_highpass(esos)
+    x = ib.families(fams, ib.T_LONG, rate)
+    yf = ib.sosfilt_runs(sos, x)[1].astype(np.float32)[:, ib.envelope_lanes(fams, efams)]
+    firsts = ib.ENV_FIRST if (bp, env) in ib.SOSFILT_ENVELOPE or (bp, env) == ib.CHAIN[2048, 1024] else ib.ENV_FIRST[:1]
+    for first in firsts:
+        what = '%s + %s from %d' % (bp, env, first)
+        ref, run = ib.envelope_runs(esos, yf[first:])
+        q = check_case(ref, run, what)
+        model = ib.sosfiltfilt(esos, yf[first:], np.float64, clamp=False, right_ext_f32=True, left_ext_f32=first > 0)
+        term = ib.extension_term(esos, yf[first:], left=first > 0) if hp else None
+        ib.assert_within(model.astype(np.float32), ref, q, what + ', float32 extensions', margin=1.0, term=term)
+
+
+@pytest.mark.parametrize('case,table', [('bp2 300-3000 Hz @ 96 kHz', 'BANDPASSES'), ('bp4 300-3000 Hz @ 48 kHz', 'BANDPASSES'),
+                                        ('lp2 20 Hz @ 96 kHz', 'ENVELOPES'), ('lp2 500 Hz @ 48 kHz', 'ENVELOPES')])
+def test_a_float32_hand_over_is_caught_and_passes_the_old_metric(case, table):
+    sos, rate, _ = ib.design(case, getattr(ib, table))
+    x = ib.families(ib.FAMILIES, ib.T_LONG, rate)
+    ref, q = ib.sosfilt_case(sos, x)
+    assert np.all(q <= ib.Q_CAP)
+    wrong = ib.wrong_f32_handover(sos, x).astype(np.float32)
+    rho = np.max(ib.ratios(wrong, ref), axis=0)
+    old = [rel_err(wrong[:, c], np.asarray(ref[:, c], dtype=np.float64)) for c in range(x.shape[1])]
+    print('%s: local %s, rel_err %s' % (case, ' '.join('%.3g' % v for v in rho), ' '.join('%.2g' % v for v in old)))
+    assert max(old) < 1e-4                                     # the old metric lets it through in every family
+    assert np.any(rho > 1.0 + ib.MARGIN*q)
+    with pytest.raises(AssertionError):
+        ib.assert_within(wrong, ref, q, case)
+
+
+def test_a_one_tile_warm_up_is_caught():
+    case = 'lp2 20 Hz @ 96 kHz'                                # the longest memory of the list: 26 tiles
+    sos, rate, _ = ib.design(case, ib.ENVELOPES)
+    x = ib.families(ib.FAMILIES, ib.T_LONG, rate)
+    ref, q = ib.sosfilt_case(sos, x)
+    wrong = ib.wrong_one_tile_warmup(sos, x).astype(np.float32)
+    rho = np.max(ib.ratios(wrong, ref), axis=0)
+    print('%s: local %s' % (case, ' '.join('%.3g' % v for v in rho)))
+    assert np.any(rho > 1.0 + ib.MARGIN*q)
+    with pytest.raises(AssertionError):
+        ib.assert_within(wrong, ref, q, case)
