@@ -248,13 +248,131 @@ class BufferedArray(object):
                  for c in range(self.channels)]
         return Events(pairs, self.rate, getattr(self, 'name', None))
 
-    def event_thresholds(self, factor, start=None, stop=None):
-        """The usual threshold of a detector, mean + factor*std of frames [start, stop) per channel (the alternative
-        songdetector.py:119-127 leaves commented out), from ONE region_stats call over the range."""
+    def event_thresholds(self, factor, start=None, stop=None, method='std'):
+        """Per-channel thresholds of a detector over frames [start, stop).  method='std': mean + factor*std (the
+        alternative songdetector.py:119-127 leaves commented out), from ONE region_stats call over the range.
+        method='histogram': threshold_estimates(start, stop), the reference's live function (songdetector.py:85-117);
+        `factor` is ignored then, as the reference ignores its own `fac`."""
+        if method == 'histogram':
+            return self.threshold_estimates(start, stop)
+        if method != 'std':
+            raise ValueError("method: 'std' or 'histogram'")
         a = self.offset if start is None else int(start)
         b = self.offset + len(self._buf()) if stop is None else int(stop)
         stats = self.region_stats([(a, b)])[0]
         return stats[:, 1] + float(factor)*stats[:, 2]
+
+    def _trace_range(self, what, start, stop):
+        """Frames [start, stop) (absolute; by default the whole buffer) relative to the buffer, for a trace."""
+        if len(self.shape) > 2:
+            raise TypeError('%s is for traces, not for spectrogram-shaped data' % what)
+        n = len(self._buf())
+        a = 0 if start is None else int(start) - self.offset
+        b = n if stop is None else int(stop) - self.offset
+        if a < 0 or b > n or b < a:
+            raise IndexError('range outside the loaded buffer')
+        return a, b
+
+    @staticmethod
+    def _histogram_edges(edges):
+        e = np.asarray(edges, dtype=np.float64).reshape(-1)
+        if len(e) < 2:
+            raise ValueError('edges: at least two values (one bin)')
+        if len(e) > 1025:
+            raise NotImplementedError('at most 1024 bins per call, got %d' % (len(e) - 1))
+        if not np.isfinite(e).all() or (np.diff(e) < 0).any():
+            raise ValueError('edges: finite, non-decreasing values')
+        return e
+
+    def _masked_bounds(self, lo, hi, pivot):
+        """(channels, 3) float64: lo, hi, pivot per channel, each given as one value or one per channel.  The default
+        pivot is the finite one of the two bounds (lo if both are), 0 if neither is."""
+        bounds = np.zeros((self.channels, 3))
+        try:
+            bounds[:, 0] = np.asarray(lo, dtype=np.float64)
+            bounds[:, 1] = np.asarray(hi, dtype=np.float64)
+            if pivot is None:
+                bounds[:, 2] = np.where(np.isfinite(bounds[:, 0]), bounds[:, 0],
+                                        np.where(np.isfinite(bounds[:, 1]), bounds[:, 1], 0.0))
+            else:
+                bounds[:, 2] = np.asarray(pivot, dtype=np.float64)
+        except ValueError:
+            raise ValueError('lo, hi, pivot: one value or one per channel')
+        if not np.isfinite(bounds[:, 2]).all():
+            raise ValueError('pivot must be finite')
+        return bounds
+
+    def histogram(self, edges, start=None, stop=None, channel=None):
+        """Amplitude histogram of frames [start, stop) (absolute, inside the current buffer; the whole buffer by default)
+        of every channel over `edges` (B + 1 finite, non-decreasing values, B <= 1024), with numpy on the host buffer:
+        int64 (channels, B + 3), or (B + 3,) for one channel.  Slots 0 .. B-1 are np.histogram's counts (bin = the
+        number of interior edges <= x, for edges[0] <= x <= edges[-1]: the last bin is closed), slot B counts the
+        samples below edges[0], B + 1 those above edges[-1], B + 2 the NaNs; a row sums to stop - start
+        (hipdsp_histogram in include/hip_dsp.h; BufferedData.histogram is the same on the device mirror).  TypeError
+        for spectrogram-shaped traces."""
+        a, b = self._trace_range('histogram', start, stop)
+        e = self._histogram_edges(edges)
+        B = len(e) - 1
+        res = np.zeros((self.channels, B + 3), dtype=np.int64)
+        block = np.asarray(self.buffer[a:b], dtype=np.float64)
+        for c in range(self.channels):
+            v = block[:, c]
+            inside = v[(v >= e[0]) & (v <= e[-1])]
+            res[c, :B] = np.bincount(np.searchsorted(e[1:-1], inside, side='right'), minlength=B)
+            res[c, B:] = np.sum(v < e[0]), np.sum(v > e[-1]), np.sum(np.isnan(v))
+        return res[channel] if channel is not None else res
+
+    def masked_stats(self, lo, hi, pivot=None, start=None, stop=None):
+        """Number, mean and std (ddof 0) of the samples with lo < x < hi (both strict; -inf / +inf switch a side off;
+        NaN and infinite samples are never selected, a NaN bound selects nothing) of frames [start, stop) of every
+        channel, and a reserved 0: (channels, 4), NaN mean and std where nothing is selected.  lo, hi and pivot are
+        each one value or one per channel.  Here numpy on the host buffer (np.mean, np.std; the pivot is checked and
+        not used); BufferedData.masked_stats is the same on the device mirror, where the sums are shifted by `pivot`
+        (hipdsp_masked_stats in include/hip_dsp.h; default: the finite one of the two bounds, 0 if neither is).
+        TypeError for spectrogram-shaped traces."""
+        a, b = self._trace_range('masked_stats', start, stop)
+        bounds = self._masked_bounds(lo, hi, pivot)
+        res = np.zeros((self.channels, 4))
+        block = np.asarray(self.buffer[a:b], dtype=np.float64)
+        with np.errstate(invalid='ignore'):
+            for c in range(self.channels):
+                v = block[:, c]
+                sel = v[(v > bounds[c, 0]) & (v < bounds[c, 1]) & np.isfinite(v)]
+                res[c, :3] = (len(sel), np.mean(sel), np.std(sel)) if len(sel) else (0, np.nan, np.nan)
+        return res
+
+    def threshold_estimates(self, start=None, stop=None):
+        """The reference's histogram threshold (threshold_estimates, songdetector.py:85-117) of frames [start, stop) of
+        an envelope-like trace, one float64 per channel, from four reductions over the range:
+          1. maxe, the maximum over all channels (one region_stats call);
+          2. per channel the histogram over b = np.linspace(0, maxe, 50); mini = the first non-empty bin, maxi = the
+             fullest bin + 1, widened by maxi - mini and clamped to 49 (on the host, from the 49 counts);
+          3. mean and std of the samples below b[maxi] (masked_stats, pivot b[maxi]);
+          4. uppermean, the mean of the samples above mean + 3*std (masked_stats);
+        the threshold is 0.5*(mean + uppermean) if uppermean > mean + 6*std, else maxe + std -- also when no sample
+        lies above mean + 3*std (uppermean is NaN and the comparison false, as in the reference).
+        Deviation: where the reference fails with an IndexError or a numpy error -- the maximum over the range NaN,
+        infinite or <= 0 (an empty range included), or a channel without a sample in [0, maxe] -- this raises a
+        ValueError that says so.  TypeError for spectrogram-shaped traces."""
+        a, b = self._trace_range('threshold_estimates', start, stop)
+        first, last = self.offset + a, self.offset + b
+        maxe = np.max(self.region_stats([(first, last)])[0][:, 4]) if b > a and self.channels > 0 else np.nan
+        if not (np.isfinite(maxe) and maxe > 0.0):
+            raise ValueError('threshold_estimates: the maximum over the range is %r; it must be finite and > 0' % float(maxe))
+        edges = np.linspace(0.0, maxe, 50)
+        counts = self.histogram(edges, first, last)[:, :49]
+        if (counts.sum(axis=1) == 0).any():
+            raise ValueError('threshold_estimates: a channel has no sample between 0 and the maximum %r' % float(maxe))
+        mini = np.argmax(counts > 0, axis=1)
+        maxi = np.argmax(counts, axis=1) + 1
+        maxi = np.minimum(maxi + (maxi - mini), 49)
+        cut = edges[maxi]
+        lower = self.masked_stats(-np.inf, cut, cut, first, last)
+        mean, std = lower[:, 1], lower[:, 2]
+        above = mean + 3.0*std
+        upper = self.masked_stats(above, np.inf, np.where(np.isfinite(above), above, 0.0), first, last)
+        with np.errstate(invalid='ignore'):
+            return np.where(upper[:, 1] > mean + 6.0*std, 0.5*(mean + upper[:, 1]), maxe + std)
 
     def __getitem__(self, key):
         if not isinstance(key, tuple):

@@ -584,6 +584,33 @@ class BufferedData(BufferedArray):
                                      thr if np.ndim(thresholds) > 0 else float(thr[0]), gap, length)
         return Events([p + self.offset for p in pairs], self.rate, self.name)
 
+    def _on_mirror(self, a, b):
+        """Can a reduction over frames [a, b) of the buffer run on the device mirror?"""
+        return self.channels > 0 and b > a and self._dev is not None and _covers(self._dev_valid, a, b)
+
+    def histogram(self, edges, start=None, stop=None, channel=None):
+        """BufferedArray.histogram on the device mirror when it is valid over the range (hipdsp_histogram: the trace is
+        read once on the device, 8*(B + 3) bytes per channel come back), else numpy on the host buffer.  Nothing is
+        read back from the mirror: the host copy stays as stale as it was."""
+        from . import hipdsp
+        a, b = self._trace_range('histogram', start, stop)
+        if not self._on_mirror(a, b):
+            return BufferedArray.histogram(self, edges, start, stop, channel)
+        res = hipdsp.histogram(self.ctx, self._dev, self._pitch(), self.channels, a, b, self._histogram_edges(edges))
+        return res[channel] if channel is not None else res
+
+    def masked_stats(self, lo, hi, pivot=None, start=None, stop=None):
+        """BufferedArray.masked_stats on the device mirror when it is valid over the range (hipdsp_masked_stats, sums
+        shifted by `pivot`; 32 bytes per channel come back), else numpy on the host buffer.  Nothing is read back from
+        the mirror: the host copy stays as stale as it was.  threshold_estimates and
+        event_thresholds(method='histogram') are BufferedArray's and run on the mirror through these calls."""
+        from . import hipdsp
+        a, b = self._trace_range('masked_stats', start, stop)
+        if not self._on_mirror(a, b):
+            return BufferedArray.masked_stats(self, lo, hi, pivot, start, stop)
+        return hipdsp.masked_stats(self.ctx, self._dev, self._pitch(), self.channels, a, b,
+                                   self._masked_bounds(lo, hi, pivot))
+
     # ---- the reference's surface (src/audian/buffereddata.py), restated --------------
     def expand_times(self, tbefore, tafter):
         """Widen this trace's own margins by what a derived trace needs; returns what the source

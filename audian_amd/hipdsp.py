@@ -650,6 +650,51 @@ def detect_events(ctx, x, x_pitch, channels, start, stop, thresholds, min_gap, m
             dthr.free()
 
 
+def histogram(ctx, x, x_pitch, channels, start, stop, edges, out=None, out_pitch=0):
+    """Amplitude histogram of x[c, start:stop] over the float64 `edges` (B + 1 finite, non-decreasing values, B <= 1024)
+    for every channel (hipdsp_histogram): np.histogram's counts in slots 0 .. B-1, then the samples below edges[0],
+    above edges[-1] and the NaNs.  Returns the (channels, B + 3) int64 host array -- all that crosses to the host -- or,
+    with `out` (a DeviceArray of int64, rows `out_pitch` elements apart, 0 = B + 3), fills it and returns it."""
+    e = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+    B, channels = len(e) - 1, int(channels)
+    dev = out if out is not None else DeviceArray(ctx, (max(1, channels), max(1, B) + 3), np.int64)
+    _count('histogram')
+    check(lib.hipdsp_histogram(ctx.handle, _p(x), int(x_pitch), channels, int(start), int(stop),
+                               e.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), B, _p(dev), int(out_pitch)))
+    if out is not None:
+        return out
+    res = dev.to_host()[:channels] if channels > 0 else np.zeros((0, B + 3), dtype=np.int64)
+    dev.free()
+    return res
+
+
+def masked_stats(ctx, x, x_pitch, channels, start, stop, bounds, out=None):
+    """Number, mean and std (ddof 0) of the samples of x[c, start:stop] with lo < x < hi, and a reserved 0, for every
+    channel (hipdsp_masked_stats).  `bounds` is (channels, 3) float64 -- lo, hi, pivot per channel -- on the host or a
+    DeviceArray.  Returns the (channels, 4) float64 host array, or, with `out` (a DeviceArray of that shape), fills it
+    and returns it without any copy."""
+    channels = int(channels)
+    dbounds = bounds
+    if not isinstance(bounds, DeviceArray):
+        b = np.ascontiguousarray(bounds, dtype=np.float64)
+        if b.shape != (channels, 3):
+            raise ValueError('bounds: (channels, 3) values lo, hi, pivot')
+        dbounds = DeviceArray.from_host(ctx, b if channels > 0 else np.zeros((1, 3)))
+    dev = out if out is not None else DeviceArray(ctx, (max(1, channels), 4), np.float64)
+    try:
+        _count('masked_stats')
+        check(lib.hipdsp_masked_stats(ctx.handle, _p(x), int(x_pitch), channels, int(start), int(stop), _p(dbounds),
+                                      _p(dev)))
+        if out is not None:
+            return out
+        return dev.to_host()[:channels] if channels > 0 else np.zeros((0, 4))
+    finally:
+        if dbounds is not bounds:
+            dbounds.free()
+        if out is None:
+            dev.free()
+
+
 def memcpy2d(ctx, dst, dst_pitch_bytes, src, src_pitch_bytes, width_bytes, height):
     check(lib.hipdsp_memcpy2d_d2d(ctx.handle, _p(dst), int(dst_pitch_bytes), _p(src),
                                   int(src_pitch_bytes), int(width_bytes), int(height)))

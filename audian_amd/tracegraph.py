@@ -166,12 +166,14 @@ class TraceGraph(object):
             trace.update_buffer(i0, i1)         # (a raw loader that is not shown does not follow update_times)
         return i0, i1
 
-    def event_thresholds(self, trace_name, factor, t0=None, t1=None):
+    def event_thresholds(self, trace_name, factor, t0=None, t1=None, method='std'):
         """mean + factor*std of the trace between t0 and t1 (by default its current buffer), one value per channel:
-        the usual threshold of a detector (songdetector.py:119-127), from one region_stats call."""
+        the usual threshold of a detector (songdetector.py:119-127), from one region_stats call.  With
+        method='histogram' the reference's histogram threshold instead (threshold_estimates, songdetector.py:85-117;
+        BufferedArray.threshold_estimates), which ignores `factor`."""
         trace = self[trace_name]
         i0, i1 = self._event_frames(trace, t0, t1)
-        return trace.event_thresholds(factor, i0, i1)
+        return trace.event_thresholds(factor, i0, i1, method=method)
 
     def detect_events(self, trace_name, thresholds, min_gap=0.0, min_duration=0.0, t0=None, t1=None):
         """Threshold events of a trace between t0 and t1 seconds (by default its current buffer): the buffer is moved

@@ -675,6 +675,75 @@ int hipdsp_detect_events(hipdsp_ctx *ctx, const float *x, int64_t x_pitch, int64
                          int64_t stop, const float *dev_thresholds, double threshold, int64_t min_gap,
                          int64_t min_len, int64_t capacity, int64_t *events, int64_t events_pitch, int64_t *counts);
 
+/* ---- amplitude histograms and moments inside an amplitude window ----------- */
+
+/* The two reductions of the reference's histogram threshold (threshold_estimates, songdetector.py:85-117): a 49-bin
+ * amplitude histogram per channel between 0 and the global maximum, mean and std of the samples below a bin edge
+ * derived from the histogram's mode, the mean of the samples above mean + 3 std, and from these 0.5*(mean + uppermean)
+ * or maxe + std.  BufferedData.threshold_estimates (audian_amd/buffereddata.py) builds that function on the two calls
+ * below and hipdsp_region_stats (for the maximum); the integer bookkeeping between them runs on the host.
+ *
+ * hipdsp_histogram.  x is planar float32, `channels` rows x_pitch elements apart (x_pitch >= stop, unless there is one
+ * channel); of every row the elements [start, stop) are looked at, 0 <= start <= stop.  host_edges is a HOST array of
+ * n_bins + 1 finite, non-decreasing float64 values e[0..B], B = n_bins, 1 <= n_bins <= 1024.  The edges travel to the
+ * kernels by value (256 per launch of a small kernel that stores them in the context scratch): the array is consumed
+ * when the call returns, there is no upload and no host synchronisation, and the call is legal inside
+ * hipdsp_graph_begin/end once the scratch is reserved (a replay counts with the edges of capture time).
+ * out is a DEVICE array (channels, n_bins + 3) of int64, out_pitch elements between channels (0 = n_bins + 3), aligned
+ * to 8 bytes; the call overwrites all n_bins + 3 slots of every channel and touches nothing else.
+ * Counts are those of np.histogram(v.astype(float64), bins=edges), which is this rule: a sample x, converted exactly to
+ * float64, is counted in a bin when e[0] <= x <= e[B], and its bin is the number of interior edges e[1..B-1] that are
+ * <= x.  So every bin is [e[i], e[i+1]), the last bin is closed on the right, and a bin of zero width is empty unless it
+ * is the last one and x == e[B].  Three more slots take the rest:
+ *   out[c][B]     samples < e[0], -inf included
+ *   out[c][B+1]   samples > e[B], +inf included
+ *   out[c][B+2]   NaN samples
+ * so every row of out sums to stop - start.  All comparisons are float64 comparisons of exactly converted samples with
+ * the edges as given (the library is built without floating-point contraction); a first guess of the bin from
+ * (x - e[0]) * B / (e[B] - e[0]) is corrected against e[k] and e[k+1] until the rule holds, so the result is exact for
+ * any edges and costs O(1) for uniform ones.
+ * HIPDSP_ERR_INVALID: a NULL ctx, host_edges or out, a decreasing or non-finite edge, n_bins < 1, negative sizes,
+ * start > stop, x_pitch < stop with more than one channel, out_pitch < n_bins + 3 (other than 0), misaligned pointers.
+ * HIPDSP_ERR_UNSUPPORTED: n_bins > 1024, more than 65535 channels.  stop == start writes zeros; channels == 0 writes
+ * nothing.  Index arithmetic is 64-bit; rows start at any 4-byte address; at most 2^31 - 1 chunks of 16384 elements
+ * per row.  The trace is read once.
+ * Uses the context scratch: 8 * (n_bins + 1) bytes (the edges) -- like hipdsp_region_stats it may not come between
+ * phase 1 and phase 2 of hipdsp_sosfilt_envelope.
+ *
+ * hipdsp_masked_stats.  x, x_pitch, channels, start, stop as above.  dev_bounds is a DEVICE array (channels, 3) of
+ * float64: lo, hi, pivot of every channel.  A sample is selected when lo < x < hi, x converted exactly to float64, both
+ * comparisons strict; lo = -inf or hi = +inf switches that side off.  NaN samples and infinite samples are never
+ * selected; a NaN bound selects nothing.  out is a DEVICE array (channels, 4) of float64, compact:
+ *   [0] the number of selected samples    [1] their mean    [2] their std (ddof 0)    [3] 0 (reserved)
+ * With nothing selected (also stop == start) [1] and [2] are NaN.  pivot must be finite ([1] and [2] mean nothing
+ * otherwise); a good pivot is a value near the selected samples, such as the finite one of the two bounds.
+ * HIPDSP_ERR_INVALID: a NULL ctx, dev_bounds or out, negative sizes, start > stop, x_pitch < stop with more than one
+ * channel, misaligned pointers.  HIPDSP_ERR_UNSUPPORTED: more than 65535 channels.  channels == 0 writes nothing.
+ * No host synchronisation, nothing is read back, legal inside hipdsp_graph_begin/end once the scratch is reserved.
+ * Uses the context scratch under the same rule: 24 bytes per channel and 16384-element chunk of [start, stop) (at
+ * least 24 bytes per channel).
+ *
+ * Accuracy contract of hipdsp_masked_stats for finite selected samples -- the one of hipdsp_region_stats with K =
+ * pivot.  The sums are pivot-shifted and carried in float64: over the n selected samples d_i = x_i - K, S1 = sum d_i,
+ * S2 = sum d_i^2, mean = K + S1/n and std^2 = max(S2/n - (S1/n)^2, 0).  For EVERY summation order of S1 and S2, with
+ * u = 2^-53, N = stop - start, g = (N+3)u / (1 - (N+3)u) (N, not n: an unselected sample adds an exact zero to both
+ * sums, which costs no accuracy but is a term of the sum), D1 = mean |d_i|, D2 = mean d_i^2 and mu, sigma^2 the exact
+ * mean and variance of the selected float32 values,
+ *     |mean - mu|             <= g*D1 + u*|mu|
+ *     |std^2 - sigma^2| = E   <= 3g*D2 + 4u*sigma^2
+ *     |std - sigma|           <= min(sqrt(E), E / sigma)
+ * and [0] is exact.
+ *
+ * Determinism, both calls: no float atomics.  The histogram's only atomics are integer adds (32-bit in LDS, one 64-bit
+ * add per non-empty bin and workgroup to out), whose sums do not depend on arrival order; the float64 sums of
+ * hipdsp_masked_stats are merged in an order fixed by the number of chunks.  The chunk grid is anchored at `start`:
+ * the same call gives the same bytes twice, and a channel's row does not depend on which other channels ride in the
+ * call. */
+int hipdsp_histogram(hipdsp_ctx *ctx, const float *x, int64_t x_pitch, int64_t channels, int64_t start, int64_t stop,
+                     const double *host_edges, int n_bins, int64_t *out, int64_t out_pitch);
+int hipdsp_masked_stats(hipdsp_ctx *ctx, const float *x, int64_t x_pitch, int64_t channels, int64_t start,
+                        int64_t stop, const double *dev_bounds, double *out);
+
 /* ---- multi-GPU exchange ---------------------------------------- */
 
 /* One process per GPU, channels sharded in contiguous blocks of the planar layout, so

@@ -176,6 +176,24 @@ for b in builds:
     logs[b['name']].append(f'{"hipdsp_detect_events, the whole envelope, min_gap 0.1 s, min_len 0.01 s":78s} {ms:8.3f} ms {4.0*S/ms/1e6:7.0f} GB/s')
     if b is builds[-1]:
         print(logs[b['name']][-1], flush=True)
+# ---- hipdsp_histogram and hipdsp_masked_stats: the whole envelope, the reference's 49 bins / the samples below a cut
+# (tools/histogram_bench.py has the concentrated envelope, the ratios to hipdsp_region_stats and the whole threshold estimate)
+for b in builds:
+    h, ctx = b['h'], b['ctx']
+    if not hasattr(h.lib, 'hipdsp_histogram'):
+        continue
+    counts = h.DeviceArray(ctx, (C, 52), np.int64)
+    bounds = h.DeviceArray.from_host(ctx, np.tile([-np.inf, 0.25, 0.25], (C, 1)))
+    moments = h.DeviceArray(ctx, (C, 4), np.float64)
+    edges = np.linspace(0.0, 1.0, 50)
+    for name, f in (('hipdsp_histogram, the whole envelope, 49 bins', lambda: h.histogram(ctx, b['buf']['de'], T, C, 0, T, edges, out=counts)),
+                    ('hipdsp_masked_stats, the whole envelope, the samples below 0.25',
+                     lambda: h.masked_stats(ctx, b['buf']['de'], T, C, 0, T, bounds, out=moments))):
+        ms = min(timed(b, f, 5) for _ in range(rounds))
+        ctx.synchronize()
+        logs[b['name']].append(f'{name:78s} {ms:8.3f} ms {4.0*S/ms/1e6:7.0f} GB/s')
+        if b is builds[-1]:
+            print(logs[b['name']][-1], flush=True)
 prefix = os.environ.get('OUT_PREFIX')
 if prefix:
     for name, lines in logs.items():
