@@ -3,19 +3,32 @@
 ``spectrogram`` / ``decibel`` (scipy.signal.spectrogram with a Hann window, constant
 detrend, density scaling) become ``hipdsp_spectrogram`` / ``hipdsp_decibel_image``."""
 
+import math
+
 import numpy as np
 
 from .buffereddata import BufferedData
 
 
+def _log10(x):
+    return math.log10(x) if x > 0 else (-math.inf if x == 0 else math.nan)
+
+
+# the C library's log10, element by element: np.log10's vector loops differ from it in the last bit of about one
+# argument in a hundred, and this function is held bit for bit to the C restatement the tests keep
+# (tests/test_decibel_bound.py)
+_log10 = np.frompyfunc(_log10, 1, 1)
+
+
 def decibel(power, ref_power=1.0, min_power=1e-20):
     """thunderlab.powerspectrum.decibel for host arrays and scalars (used by the
     once-per-trace colour-range estimate and by cursors; the image path is on the
-    device): 10*log10(power/ref_power), -inf at or below min_power."""
+    device): 10*log10(power/ref_power), -inf at or below min_power, NaN stays NaN."""
     p = np.asarray(power, dtype=np.float64)
     out = np.full(p.shape, -np.inf)
-    m = p > min_power
-    out[m] = 10.0*np.log10(p[m]/ref_power)
+    m = ~(p <= min_power)
+    with np.errstate(over='ignore', under='ignore'):
+        out[m] = 10.0*_log10(p[m]/ref_power).astype(np.float64)
     return out if out.ndim else float(out)
 
 

@@ -20,6 +20,7 @@
 // Rows start at any 4-byte address (nfreq is odd, views begin at any frame): dword loads only, no alignment assumed;
 // nothing outside the merged segments of a row is touched.  Index arithmetic on the slab is 64-bit.
 #include "common.h"
+#include "decibel.h"
 
 namespace {
 
@@ -31,16 +32,11 @@ struct BandArgs {
     int n_bands, n_segs;
 };
 
-// the arithmetic of hipdsp_decibel (elementwise.hip: decibel_of), so that dB here is bit for bit decibel(linear)
-__device__ __forceinline__ float band_decibel(float v, float inv_ref, float min_power)
-{
-    return (v <= min_power) ? -INFINITY : 10.0f * log10f(v * inv_ref);
-}
-
-__device__ __forceinline__ float band_value(double sum, double scale, int db, float inv_ref, float min_power)
+// dB in the arithmetic of hipdsp_decibel (decibel.h: decibel_of), so that dB here is bit for bit decibel(linear)
+__device__ __forceinline__ float band_value(double sum, double scale, int db, const DbArgs &dba)
 {
     const float v = (float)(scale * sum);
-    return db ? band_decibel(v, inv_ref, min_power) : v;
+    return db ? decibel_of(v, dba) : v;
 }
 
 template <int NB>
@@ -53,8 +49,8 @@ __device__ __forceinline__ void band_add(double (&acc)[NB], const BandArgs &a, i
 
 template <int NB, int TPF>
 __global__ __launch_bounds__(256) void band_rows_kernel(const float *__restrict__ spec, long long spec_pitch, long long frames,
-                                                        int nfreq, BandArgs a, double scale, int db, float inv_ref,
-                                                        float min_power, float *__restrict__ out, long long out_pitch,
+                                                        int nfreq, BandArgs a, double scale, int db, DbArgs dba,
+                                                        float *__restrict__ out, long long out_pitch,
                                                         long long out_band_pitch)
 {
     constexpr int RPB = 256 / TPF;                      // rows (frames of one channel) per workgroup
@@ -101,7 +97,7 @@ __global__ __launch_bounds__(256) void band_rows_kernel(const float *__restrict_
 #pragma unroll
         for (int b = 0; b < NB; b++)
             if (b < a.n_bands)
-                out[b * out_band_pitch + c * out_pitch + f] = band_value(acc[b], scale, db, inv_ref, min_power);
+                out[b * out_band_pitch + c * out_pitch + f] = band_value(acc[b], scale, db, dba);
     }
 }
 
@@ -109,8 +105,8 @@ constexpr int SHORT_FRAMES = 256, SHORT_BINS = 32;
 
 template <int NB>
 __global__ __launch_bounds__(256) void band_short_kernel(const float *__restrict__ spec, long long spec_pitch, long long frames,
-                                                         int nfreq, BandArgs a, double scale, int db, float inv_ref,
-                                                         float min_power, float *__restrict__ out, long long out_pitch,
+                                                         int nfreq, BandArgs a, double scale, int db, DbArgs dba,
+                                                         float *__restrict__ out, long long out_pitch,
                                                          long long out_band_pitch)
 {
     __shared__ float tile[SHORT_FRAMES * (SHORT_BINS + 1)];      // +1: a lane walks its own row, rows on different banks
@@ -153,30 +149,30 @@ __global__ __launch_bounds__(256) void band_short_kernel(const float *__restrict
 #pragma unroll
         for (int b = 0; b < NB; b++)
             if (b < a.n_bands)
-                out[b * out_band_pitch + c * out_pitch + f0 + tid] = band_value(acc[b], scale, db, inv_ref, min_power);
+                out[b * out_band_pitch + c * out_pitch + f0 + tid] = band_value(acc[b], scale, db, dba);
     }
 }
 
 template <int NB>
 int band_launch(hipdsp_ctx *ctx, const float *spec, long long spec_pitch, long long channels, long long frames, int nfreq,
-                const BandArgs &a, double scale, int db, float inv_ref, float min_power, float *out, long long out_pitch,
+                const BandArgs &a, double scale, int db, const DbArgs &dba, float *out, long long out_pitch,
                 long long out_band_pitch)
 {
     if (nfreq <= 256) {
         const dim3 grid((unsigned)((frames + SHORT_FRAMES - 1) / SHORT_FRAMES), (unsigned)channels);
         hipLaunchKernelGGL(band_short_kernel<NB>, grid, dim3(256), 0, ctx->stream, spec, spec_pitch, frames, nfreq, a,
-                           scale, db, inv_ref, min_power, out, out_pitch, out_band_pitch);
+                           scale, db, dba, out, out_pitch, out_band_pitch);
         return hd_launch_status("band_short_kernel");
     }
     if (nfreq < 8192) {
         const dim3 grid((unsigned)((frames + 3) / 4), (unsigned)channels);
         hipLaunchKernelGGL((band_rows_kernel<NB, 64>), grid, dim3(256), 0, ctx->stream, spec, spec_pitch, frames, nfreq, a,
-                           scale, db, inv_ref, min_power, out, out_pitch, out_band_pitch);
+                           scale, db, dba, out, out_pitch, out_band_pitch);
         return hd_launch_status("band_rows_kernel<64>");
     }
     const dim3 grid((unsigned)frames, (unsigned)channels);
     hipLaunchKernelGGL((band_rows_kernel<NB, 256>), grid, dim3(256), 0, ctx->stream, spec, spec_pitch, frames, nfreq, a,
-                       scale, db, inv_ref, min_power, out, out_pitch, out_band_pitch);
+                       scale, db, dba, out, out_pitch, out_band_pitch);
     return hd_launch_status("band_rows_kernel<256>");
 }
 
@@ -235,13 +231,13 @@ extern "C" int hipdsp_band_power(hipdsp_ctx *ctx, const float *spec, int64_t spe
         }
     }
     HD_CHECK_HIP(hipSetDevice(ctx->device));
-    const float inv_ref = db ? (float)(1.0 / ref_power) : 1.0f;
+    const DbArgs dba = db ? db_args(ref_power, min_power) : db_args(1.0, 0.0);
     if (n_bands == 1)
-        return band_launch<1>(ctx, spec, spec_pitch, channels, frames, (int)nfreq, a, scale, db, inv_ref, (float)min_power,
+        return band_launch<1>(ctx, spec, spec_pitch, channels, frames, (int)nfreq, a, scale, db, dba,
                               out, out_pitch, out_band_pitch);
     if (n_bands <= 4)
-        return band_launch<4>(ctx, spec, spec_pitch, channels, frames, (int)nfreq, a, scale, db, inv_ref, (float)min_power,
+        return band_launch<4>(ctx, spec, spec_pitch, channels, frames, (int)nfreq, a, scale, db, dba,
                               out, out_pitch, out_band_pitch);
-    return band_launch<16>(ctx, spec, spec_pitch, channels, frames, (int)nfreq, a, scale, db, inv_ref, (float)min_power,
+    return band_launch<16>(ctx, spec, spec_pitch, channels, frames, (int)nfreq, a, scale, db, dba,
                            out, out_pitch, out_band_pitch);
 }

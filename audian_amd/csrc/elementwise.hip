@@ -1,6 +1,7 @@
 // Element-wise and layout kernels of libhip_dsp (gfx950): decibel, the
 // (T,C) <-> planar conversions at the drop-in edge, and the synthetic generator.
 #include "common.h"
+#include "decibel.h"
 #include <cmath>
 
 namespace {
@@ -8,31 +9,25 @@ namespace {
 // one 16-byte access per thread and no loop (the form that reaches the device's copy rate, see copy_probe_kernel;
 // as a grid-stride loop of single floats it ran at 5.4 TB/s); 4-byte aligned vectors: any pointer will do
 typedef float db_f4 __attribute__((ext_vector_type(4), aligned(4)));
-__device__ __forceinline__ float decibel_of(float v, float inv_ref, float min_power)
-{
-    return (v <= min_power) ? -INFINITY : 10.0f * log10f(v * inv_ref);
-}
-__global__ __launch_bounds__(256) void decibel_kernel(const float *__restrict__ p, float *__restrict__ out, long long n,
-                                                      float inv_ref, float min_power)
+__global__ __launch_bounds__(256) void decibel_kernel(const float *__restrict__ p, float *__restrict__ out, long long n, DbArgs a)
 {
     const long long n4 = n / 4;
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i < n4) {
         const db_f4 v = *reinterpret_cast<const db_f4 *>(p + 4 * i);
         db_f4 r;
-        r.x = decibel_of(v.x, inv_ref, min_power); r.y = decibel_of(v.y, inv_ref, min_power);
-        r.z = decibel_of(v.z, inv_ref, min_power); r.w = decibel_of(v.w, inv_ref, min_power);
+        r.x = decibel_of(v.x, a); r.y = decibel_of(v.y, a);
+        r.z = decibel_of(v.z, a); r.w = decibel_of(v.w, a);
         *reinterpret_cast<db_f4 *>(out + 4 * i) = r;
     } else if (i == n4) {
-        for (long long k = 4 * n4; k < n; k++) out[k] = decibel_of(p[k], inv_ref, min_power);
+        for (long long k = 4 * n4; k < n; k++) out[k] = decibel_of(p[k], a);
     }
 }
 
 // (rows, cols) -> (cols, rows) with optional dB, 32x32 LDS tiles (+1 pad).
 template <bool DB>
 __global__ __launch_bounds__(256) void transpose_kernel(const float *__restrict__ src, float *__restrict__ dst,
-                                                        long long rows, long long cols, float inv_ref,
-                                                        float min_power)
+                                                        long long rows, long long cols, DbArgs a)
 {
     __shared__ float tile[32][33];
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;      // 32 x 8
@@ -43,7 +38,7 @@ __global__ __launch_bounds__(256) void transpose_kernel(const float *__restrict_
         float v = 0.f;
         if (r < rows && c < cols) {
             v = src[r * cols + c];
-            if (DB) v = (v <= min_power) ? -INFINITY : 10.0f * log10f(v * inv_ref);
+            if (DB) v = decibel_of(v, a);
         }
         tile[ty + 8 * k][tx] = v;
     }
@@ -68,7 +63,7 @@ template <int CPB>
 __global__ __launch_bounds__(256) void db_image_decimate_kernel(const float *__restrict__ src,
                                                                 float *__restrict__ dst, long long start,
                                                                 long long stop, long long step, long long ncols,
-                                                                long long F, float inv_ref, float min_power)
+                                                                long long F, DbArgs db)
 {
     __shared__ float tile[CPB][33];
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;      // 32 bins x 8 columns at a time
@@ -89,7 +84,7 @@ __global__ __launch_bounds__(256) void db_image_decimate_kernel(const float *__r
                 v = db_np_max(db_np_max(db_np_max(db_np_max(v, w0), w1), w2), w3);
             }
             for (; r < b; r++) v = db_np_max(v, src[r * F + f]);
-            v = (v <= min_power) ? -INFINITY : 10.0f * log10f(v * inv_ref);
+            v = decibel_of(v, db);
         }
         tile[ty + 8 * k][tx] = v;
     }
@@ -443,8 +438,7 @@ __global__ __launch_bounds__(256) void mean_spectrum_partial(const float *__rest
 }
 
 __global__ __launch_bounds__(256) void mean_spectrum_finish(const double *__restrict__ partial, long long F,
-                                                            int nsplit, double inv_n, float inv_ref,
-                                                            float min_power, float floor_db,
+                                                            int nsplit, double inv_n, DbArgs db, float floor_db,
                                                             float *__restrict__ out)
 {
     const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -452,7 +446,7 @@ __global__ __launch_bounds__(256) void mean_spectrum_finish(const double *__rest
     double acc = 0.0;
     for (int s = 0; s < nsplit; s++) acc += partial[(long long)s * F + f];
     const float p = (float)(acc * inv_n);
-    float d = (p <= min_power) ? -INFINITY : 10.0f * log10f(p * inv_ref);
+    const float d = decibel_of(p, db);
     out[f] = d < floor_db ? floor_db : d;
 }
 
@@ -678,7 +672,7 @@ int hipdsp_decibel(hipdsp_ctx *ctx, const float *p, float *out, int64_t n, doubl
     const long long blocks = (n / 4 + 1 + 255) / 256;            // one thread per four values, one more for the tail
     HD_REQUIRE(blocks <= 0x7fffffffLL, "grid too large");
     hipLaunchKernelGGL(decibel_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, p, out,
-                       (long long)n, (float)(1.0 / ref_power), (float)min_power);
+                       (long long)n, db_args(ref_power, min_power));
     return hd_launch_status("decibel_kernel");
 }
 
@@ -694,7 +688,7 @@ int hipdsp_decibel_image(hipdsp_ctx *ctx, const float *spec_tf, float *image_ft,
     HD_CHECK_HIP(hipSetDevice(ctx->device));
     dim3 grid((unsigned)((nfreq + 31) / 32), (unsigned)((frames + 31) / 32));
     hipLaunchKernelGGL(transpose_kernel<true>, grid, dim3(256), 0, ctx->stream, spec_tf, image_ft,
-                       (long long)frames, (long long)nfreq, (float)(1.0 / ref_power), (float)min_power);
+                       (long long)frames, (long long)nfreq, db_args(ref_power, min_power));
     return hd_launch_status("transpose_kernel");
 }
 
@@ -718,11 +712,11 @@ int hipdsp_decibel_image_decimate(hipdsp_ctx *ctx, const float *spec_tf, float *
     if (cpb == 8)
         hipLaunchKernelGGL(db_image_decimate_kernel<8>, grid, dim3(256), 0, ctx->stream, spec_tf, image_fc,
                            (long long)start, (long long)stop, (long long)step, ncols, (long long)nfreq,
-                           (float)(1.0 / ref_power), (float)min_power);
+                           db_args(ref_power, min_power));
     else
         hipLaunchKernelGGL(db_image_decimate_kernel<32>, grid, dim3(256), 0, ctx->stream, spec_tf, image_fc,
                            (long long)start, (long long)stop, (long long)step, ncols, (long long)nfreq,
-                           (float)(1.0 / ref_power), (float)min_power);
+                           db_args(ref_power, min_power));
     return hd_launch_status("db_image_decimate_kernel");
 }
 
@@ -969,7 +963,7 @@ int hipdsp_mean_spectrum_db(hipdsp_ctx *ctx, const float *spec_tf, int64_t nfreq
     rc = hd_launch_status("mean_spectrum_partial");
     if (rc != HIPDSP_OK) return rc;
     hipLaunchKernelGGL(mean_spectrum_finish, dim3(gx), dim3(256), 0, ctx->stream, (const double *)work,
-                       (long long)nfreq, nsplit, 1.0 / (double)n, (float)(1.0 / ref_power), (float)min_power,
+                       (long long)nfreq, nsplit, 1.0 / (double)n, db_args(ref_power, min_power),
                        (float)floor_db, out);
     return hd_launch_status("mean_spectrum_finish");
 }

@@ -414,7 +414,17 @@ int hipdsp_spectrogram(hipdsp_ctx *ctx, const float *x, int64_t x_pitch, int64_t
 
 /* thunderlab.powerspectrum.decibel (specitem.py:28,36; spectrogramplot.py:159;
  * bufferedspectrogram.py:116-117): out = 10*log10(p/ref_power), -inf where
- * p <= min_power. */
+ * p <= min_power.  The same rules hold for every entry point that takes ref_power and min_power
+ * (the two image calls below, hipdsp_mean_spectrum_db, hipdsp_band_power with db):
+ *  - the threshold is compared as written, p against the double min_power: a power equal to
+ *    (float)min_power is finite when that cast rounded up (1e-7, 0.1, 1e-10 do).  NaN stays NaN,
+ *    +inf gives +inf;
+ *  - ref_power is any positive finite double.  Where p * (float)(1/ref_power) is a normal float the
+ *    result is 10*log10f of that product (at ref_power == 1 of p itself): within
+ *    a*(10/ln 10)*2^-24 + 3 ulp of the exact value, a = 2 roundings of the argument, 0 at
+ *    ref_power == 1.  Elsewhere -- a reciprocal or product outside float32's normal range, a
+ *    denormal p -- the quotient is taken in float64 and the result is within 1 ulp.
+ * tests/decibel_bound.py holds every element to this. */
 int hipdsp_decibel(hipdsp_ctx *ctx, const float *p, float *out, int64_t n, double ref_power,
                    double min_power);
 /* SpecItem.update_plot (specitem.py:36): decibel(buffer[:, ch, :].T) -- one
