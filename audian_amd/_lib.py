@@ -142,6 +142,8 @@ _SIGNATURES = {
     'hipdsp_fir_bank': ([_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _vp, _i64, _i64], _int),
     'hipdsp_region_stats': ([_vp, _vp, _i64, _i64, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _int, _vp], _int),
     'hipdsp_detect_events': ([_vp, _vp, _i64, _i64, _i64, _i64, _vp, _dbl, _i64, _i64, _i64, _vp, _i64, _vp], _int),
+    'hipdsp_find_peaks': ([_vp, _vp, _i64, _i64, _i64, _i64, _vp, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _i64, _i64, _vp, _i64, _vp, _i64,
+                           _vp], _int),
     'hipdsp_histogram': ([_vp, _vp, _i64, _i64, _i64, _i64, ctypes.POINTER(_dbl), _int, _vp, _i64], _int),
     'hipdsp_masked_stats': ([_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp], _int),
     'hipdsp_comm_unique_id': ([_vp], _int),

@@ -248,6 +248,48 @@ class BufferedArray(object):
                  for c in range(self.channels)]
         return Events(pairs, self.rate, getattr(self, 'name', None))
 
+    def _peak_border(self, value, what, open_border):
+        """One side of a condition of find_peaks for every channel: None (open), a number or one per channel."""
+        if value is None:
+            return np.full(self.channels, open_border)
+        v = np.asarray(value, dtype=np.float64)
+        if v.ndim > 0 and v.shape != (self.channels,):
+            raise ValueError('%s: a number, a (min, max) pair, or one value per channel in either place' % what)
+        return np.broadcast_to(v, (self.channels,)).copy()
+
+    def _peak_arguments(self, height, threshold, prominence, wlen, start, stop):
+        """((channels, 6) float64 borders hmin, hmax, tmin, tmax, pmin, pmax with -inf / +inf for an open one, wlen in
+        frames (0: the whole range), first, last relative to the buffer).  A condition is None, the lower border, or a
+        (min, max) tuple or list of two; a border is None, a number or an array of one value per channel."""
+        a, b = self._trace_range('find_peaks', start, stop)
+        borders = np.zeros((self.channels, 6))
+        for k, (cond, what) in enumerate(((height, 'height'), (threshold, 'threshold'), (prominence, 'prominence'))):
+            lo, hi = cond if isinstance(cond, (tuple, list)) and len(cond) == 2 else (cond, None)
+            borders[:, 2*k] = self._peak_border(lo, what, -np.inf)
+            borders[:, 2*k + 1] = self._peak_border(hi, what, np.inf)
+        frames = 0
+        if wlen is not None:
+            frames = int(np.ceil(float(wlen)*self.rate))
+            if frames <= 1:
+                raise ValueError('wlen must be larger than one frame, it is %g frames' % (float(wlen)*self.rate))
+        return borders, frames, a, b
+
+    def find_peaks(self, height=None, threshold=None, prominence=None, wlen=None, start=None, stop=None):
+        """Peaks of frames [start, stop) (absolute, inside the current buffer; the whole buffer by default) of every
+        channel, with numpy on the host buffer: scipy.signal.find_peaks with its height, threshold, prominence and wlen
+        arguments on the float32 samples (peaks.py; the definition: hipdsp_find_peaks in include/hip_dsp.h;
+        BufferedData.find_peaks is the same on the device mirror).  No distance, width or plateau_size.  Every
+        condition is None, a number (the lower border), a (min, max) pair with None for an open side, or arrays of one
+        value per channel in either place (as event_thresholds gives them).  `wlen` is in seconds, ceil(wlen*rate)
+        frames; ValueError when that is <= 1, as in scipy.  TypeError for spectrogram-shaped traces.  Returns a Peaks
+        object of absolute frame indices."""
+        from .peaks import Peaks, host_find_peaks
+        borders, frames, a, b = self._peak_arguments(height, threshold, prominence, wlen, start, stop)
+        buf = self.buffer
+        results = [host_find_peaks(buf[a:b, c], borders[c, 0:2], borders[c, 2:4], borders[c, 4:6], frames,
+                                   first=self.offset + a) for c in range(self.channels)]
+        return Peaks(results, self.rate, getattr(self, 'name', None))
+
     def event_thresholds(self, factor, start=None, stop=None, method='std'):
         """Per-channel thresholds of a detector over frames [start, stop).  method='std': mean + factor*std (the
         alternative songdetector.py:119-127 leaves commented out), from ONE region_stats call over the range.

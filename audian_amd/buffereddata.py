@@ -588,6 +588,22 @@ class BufferedData(BufferedArray):
         """Can a reduction over frames [a, b) of the buffer run on the device mirror?"""
         return self.channels > 0 and b > a and self._dev is not None and _covers(self._dev_valid, a, b)
 
+    def find_peaks(self, height=None, threshold=None, prominence=None, wlen=None, start=None, stop=None):
+        """BufferedArray.find_peaks on the device mirror when it is valid over the range (hipdsp_find_peaks: one call
+        that counts, one that stores; the counts, the positions and 32 bytes of properties per peak come back), else
+        numpy on the host buffer.  Nothing is read back from the mirror: the host copy stays as stale as it was.
+        Returns a Peaks object of absolute frame indices."""
+        from . import hipdsp
+        from .peaks import Peaks
+        borders, frames, a, b = self._peak_arguments(height, threshold, prominence, wlen, start, stop)
+        if not self._on_mirror(a, b):
+            return BufferedArray.find_peaks(self, height, threshold, prominence, wlen, start, stop)
+        same = bool((borders == borders[0]).all())
+        results = hipdsp.find_peaks(self.ctx, self._dev, self._pitch(), self.channels, a, b,
+                                    borders[0] if same else borders, frames)
+        shift = np.array([0.0, 0.0, self.offset, self.offset])
+        return Peaks([(pos + self.offset, props + shift) for pos, props in results], self.rate, self.name)
+
     def histogram(self, edges, start=None, stop=None, channel=None):
         """BufferedArray.histogram on the device mirror when it is valid over the range (hipdsp_histogram: the trace is
         read once on the device, 8*(B + 3) bytes per channel come back), else numpy on the host buffer.  Nothing is

@@ -650,6 +650,71 @@ def detect_events(ctx, x, x_pitch, channels, start, stop, thresholds, min_gap, m
             dthr.free()
 
 
+PEAKS_CHUNK = 4096                      # samples per chunk of hipdsp_find_peaks (csrc/peaks.hip: PK_CHUNK), anchored at start
+PEAKS_BLOCKS = (64, 4096, 262144)       # samples per entry of the three levels of its min/max table
+
+
+def find_peaks_into(ctx, x, x_pitch, channels, start, stop, borders, wlen, capacity, peaks, props, counts, peaks_pitch=0,
+                    props_pitch=0):
+    """One hipdsp_find_peaks launch, everything staying on the device: `peaks` (channels, capacity) int64 (None with
+    capacity 0), `props` (channels, capacity, 4) float64 or None and `counts` (channels,) int64 are DeviceArrays;
+    `borders` is hmin, hmax, tmin, tmax, pmin, pmax for all channels (-inf / +inf: open) or a DeviceArray
+    (channels, 6) of float64."""
+    per_channel = isinstance(borders, DeviceArray) or hasattr(borders, 'data_ptr')
+    by_value = [0.0]*6 if per_channel else [float(b) for b in borders]
+    if len(by_value) != 6:
+        raise ValueError('borders: hmin, hmax, tmin, tmax, pmin, pmax')
+    _count('find_peaks')
+    check(lib.hipdsp_find_peaks(ctx.handle, _p(x), int(x_pitch), int(channels), int(start), int(stop),
+                                _p(borders if per_channel else None), *by_value, int(wlen), int(capacity), _p(peaks),
+                                int(peaks_pitch), _p(props), int(props_pitch), _p(counts)))
+
+
+def find_peaks(ctx, x, x_pitch, channels, start, stop, conditions, wlen=0, props=True, capacity=None):
+    """Peaks of x[c, start:stop] (hipdsp_find_peaks: scipy.signal.find_peaks with height, threshold, prominence and
+    wlen; no distance, width or plateau_size).  `conditions` is hmin, hmax, tmin, tmax, pmin, pmax (-inf / +inf: an
+    open border) for all channels, or (channels, 6) of them; `wlen` is in samples, 0 or 1 the whole range.  Returns a
+    list of `channels` (positions, properties) pairs: (K,) int64 row positions, ascending, and (K, 4) float64 of
+    height, prominence, left base, right base (None with props=False).  With capacity=None a first call counts only
+    and a second one stores with the largest count as capacity; with a number, at most that many peaks per channel
+    come back from one call.  Only the counts and the written entries cross to the host."""
+    channels = int(channels)
+    if channels <= 0:
+        return []
+    cond = np.asarray(conditions, dtype=np.float64)
+    if cond.shape not in ((6,), (channels, 6)):
+        raise ValueError('conditions: six borders, or six per channel')
+    dcond = DeviceArray.from_host(ctx, cond) if cond.ndim == 2 else None
+    borders = dcond if dcond is not None else cond
+    dcounts = DeviceArray(ctx, (channels,), np.int64)
+    dpeaks = dprops = None
+    try:
+        if capacity is None:
+            find_peaks_into(ctx, x, x_pitch, channels, start, stop, borders, wlen, 0, None, None, dcounts)
+            cap = int(dcounts.to_host().max())
+        else:
+            cap = int(capacity)
+        if cap > 0:
+            dpeaks = DeviceArray(ctx, (channels, cap), np.int64)
+            dprops = DeviceArray(ctx, (channels, cap, 4), np.float64) if props else None
+        if cap > 0 or capacity is not None:
+            find_peaks_into(ctx, x, x_pitch, channels, start, stop, borders, wlen, cap, dpeaks, dprops, dcounts)
+        counts = dcounts.to_host()
+        out = []
+        for c in range(channels):
+            k = min(int(counts[c]), cap)
+            pos = dpeaks.view(c*cap, (k,)).to_host() if k > 0 else np.zeros(0, dtype=np.int64)
+            pr = None
+            if props:
+                pr = dprops.view(c*cap*4, (k, 4)).to_host() if k > 0 else np.zeros((0, 4))
+            out.append((pos, pr))
+        return out
+    finally:
+        for d in (dcounts, dcond, dpeaks, dprops):
+            if d is not None:
+                d.free()
+
+
 def histogram(ctx, x, x_pitch, channels, start, stop, edges, out=None, out_pitch=0):
     """Amplitude histogram of x[c, start:stop] over the float64 `edges` (B + 1 finite, non-decreasing values, B <= 1024)
     for every channel (hipdsp_histogram): np.histogram's counts in slots 0 .. B-1, then the samples below edges[0],

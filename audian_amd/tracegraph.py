@@ -185,6 +185,23 @@ class TraceGraph(object):
         i0, i1 = self._event_frames(trace, t0, t1)
         return trace.detect_events(thresholds, min_gap, min_duration, i0, i1)
 
+    def find_peaks(self, trace_name, height=None, threshold=None, prominence=None, wlen=None, t0=None, t1=None):
+        """Peaks of a trace between t0 and t1 seconds (by default its current buffer): the buffers are moved as for
+        detect_events, then the trace finds its peaks (BufferedData.find_peaks: on its device mirror when it has one;
+        scipy.signal.find_peaks with height, threshold, prominence and wlen, `wlen` in seconds).  Returns a Peaks
+        object of absolute frame indices."""
+        trace = self[trace_name]
+        i0, i1 = self._event_frames(trace, t0, t1)
+        return trace.find_peaks(height, threshold, prominence, wlen, i0, i1)
+
+    @staticmethod
+    def mark_peaks(analyzer, name, peaks):
+        """Fill the analyzer's point events `name` (Analyzer.make_trace_events) with the peaks: (times, heights) of
+        every channel, whatever `name` held before erased."""
+        analyzer.set_events(name, -1, [], [])
+        for c in range(min(peaks.channels, len(analyzer.events[name]))):
+            analyzer.add_events(name, c, *peaks.points(c))
+
     def analyze_events(self, events, channels=None):
         """Fill the analyzers' tables with the regions of the events, channel by channel: every event is analyzed on
         its own channel only, so StatisticsAnalyzer gets one row per event (songdetector.py:141-143 analyzes each

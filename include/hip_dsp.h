@@ -685,6 +685,69 @@ int hipdsp_detect_events(hipdsp_ctx *ctx, const float *x, int64_t x_pitch, int64
                          int64_t stop, const float *dev_thresholds, double threshold, int64_t min_gap,
                          int64_t min_len, int64_t capacity, int64_t *events, int64_t events_pitch, int64_t *counts);
 
+/* ---- peak detection --------------------------------------------------------- */
+
+/* Local maxima of a device-resident trace with their prominences: the other kind of event of the reference, "Events
+ * are channel specific points. Plotted as dot at data amplitude. Many events per label. Result from some analysis."
+ * (README.md:113-117), found as its songdetector.py finds them, sig.find_peaks(envelopes[:,c]) (songdetector.py:
+ * 110-115).  The call is scipy.signal.find_peaks with its height, threshold, prominence and wlen arguments (pinned to
+ * scipy 1.15.3 by tests/golden/find_peaks.npz).  distance, width, rel_height and plateau_size are NOT part of it:
+ * distance is a greedy pass in order of height that scipy applies before the prominence; it belongs on a compacted
+ * list and needs an entry point of its own.  thunderlab's detect_peaks is neither in the reference tree nor in this
+ * image: parity with it is unpinned.  The contract is the definition below; tests/peaks_definition.py restates it.
+ * x is planar float32, `channels` rows x_pitch elements apart (x_pitch >= stop, unless there is one channel); of every
+ * row the elements v = x[c, start:stop], n = stop - start, are looked at, 0 <= start <= stop.  Every sample is
+ * converted exactly to float64 and every comparison is a float64 comparison.  Per row:
+ *   1. A run of equal samples v[l..r] (l <= r) is a peak when l >= 1, r <= n-2, v[l-1] < v[l] and v[r+1] < v[r]; its
+ *      position is m = (l + r) / 2, rounded down.  The first and the last sample of the range are never peaks, nor is a
+ *      run that reaches either end.  A NaN is never a peak and neither is a sample next to one; -0.0 == 0.0.
+ *   2. Height h = v[m]: kept when hmin <= h <= hmax.
+ *   3. Threshold tl = h - v[m-1], tr = h - v[m+1]: kept when tmin <= min(tl, tr) and max(tl, tr) <= tmax, a NaN
+ *      difference (inf - inf) failing either comparison as in numpy.
+ *   4. Prominence, scipy's peak_prominences.  lo = 0 and hi = n-1; with wlen >= 2, lo = max(m - wlen/2, 0) and hi =
+ *      min(m + wlen/2, n-1) (wlen/2 rounded down; wlen 0 and 1 mean the whole range).  Left: walk i = m, m-1, ... while
+ *      i >= lo and v[i] <= h (a NaN or a higher sample stops the walk); left_min is the minimum of the samples walked,
+ *      left_base its position, of equal minima the one nearest to m, and m itself if nothing lower than h was walked.
+ *      Right: the same with i = m, m+1, ... while i <= hi.  prominence = h - max(left_min, right_min), a float64
+ *      subtraction; kept when pmin <= prominence <= pmax.
+ *   5. A border that is -inf (lower) or +inf (upper) is open: that comparison is not made.  So a NaN prominence (it
+ *      arises only for a +inf plateau wider than wlen) passes open borders and fails any real one; a NaN border keeps
+ *      nothing; with all six borders open every local maximum is a peak.
+ *   6. Peaks come out in ascending position; positions and bases are positions in the row, not relative to start.
+ * The six borders hmin, hmax, tmin, tmax, pmin, pmax of channel c are dev_borders[6*c .. 6*c + 5] (a DEVICE array
+ * (channels, 6) of float64) or, with dev_borders == NULL, the six arguments for all channels.
+ * Output: counts is a DEVICE array of `channels` int64 and receives the number of peaks of every row, also when that
+ * exceeds capacity.  peaks is a DEVICE array (channels, capacity) int64, peaks_pitch elements between channels (0 =
+ * capacity).  props (optional, may be NULL) is a DEVICE array (channels, capacity, 4) float64, props_pitch elements
+ * between channels (0 = 4*capacity), of [height, prominence, left_base, right_base] (the bases are exact in float64).
+ * Only the first min(count, capacity) entries of a channel are written, nothing beyond them is touched.  capacity == 0
+ * with peaks == NULL is legal and gives the counts only (props is ignored then).  stop == start gives zero counts and
+ * writes nothing else; channels == 0 writes nothing.
+ * HIPDSP_ERR_INVALID: a NULL ctx, counts or (with capacity > 0) peaks, negative sizes, a negative wlen, start > stop,
+ * x_pitch < stop with more than one channel, peaks_pitch < capacity, props_pitch < 4*capacity, misaligned pointers.
+ * HIPDSP_ERR_UNSUPPORTED: more than 65535 channels or stop - start > 2^40 elements per call.  Index arithmetic is
+ * 64-bit; rows start at any 4-byte address.
+ * No host synchronisation, nothing is read back, legal inside hipdsp_graph_begin/end once the scratch is reserved.
+ * Uses the context scratch: 2584 bytes per channel and 4096-element chunk of [start, stop) (four words of bits per 64
+ * samples: rise, fall, equal, kept; a float minimum and maximum per 64 samples and per chunk; two 8-byte carries per
+ * chunk) plus 8 bytes per channel and 64 chunks (the top of the min/max table) -- 0.63 bytes per sample, whatever the
+ * number of peaks.  Like hipdsp_region_stats it may not come between phase 1 and phase 2 of hipdsp_sosfilt_envelope.
+ * Work: the trace is read once for the maxima.  The prominence search runs only for peaks that passed height and
+ * threshold, and only when a prominence border is closed (in the counting pass) or props is given (in the storing
+ * pass, for the peaks kept and below capacity); with open prominence borders and no props no search runs and the
+ * min/max table is not built.  A search is one thread's: per side it reads at most 127 samples, 126 + 126 entries of
+ * the two lower table levels (64 and 4096 samples) and (stop - start) / 262144 entries of the top level, then 192
+ * values to place the base -- some 800 reads per side at 2^26 samples, which the highest peaks of a row pay and a
+ * typical peak of white noise (a higher sample a few samples away) does not.  The lanes of a wave search in turn for
+ * the peaks of their 64 samples, so a wave takes as long as its slowest lane.
+ * Determinism: the slot of every peak comes from prefix scans over the chunks and its rank inside its chunk; there is
+ * no atomic and no float reduction whose order could vary (minima and maxima are exact).  The same call gives the same
+ * bytes twice, and a channel's result does not depend on which other channels ride in the call. */
+int hipdsp_find_peaks(hipdsp_ctx *ctx, const float *x, int64_t x_pitch, int64_t channels, int64_t start, int64_t stop,
+                      const double *dev_borders, double hmin, double hmax, double tmin, double tmax, double pmin,
+                      double pmax, int64_t wlen, int64_t capacity, int64_t *peaks, int64_t peaks_pitch, double *props,
+                      int64_t props_pitch, int64_t *counts);
+
 /* ---- amplitude histograms and moments inside an amplitude window ----------- */
 
 /* The two reductions of the reference's histogram threshold (threshold_estimates, songdetector.py:85-117): a 49-bin

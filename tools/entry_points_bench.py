@@ -194,6 +194,19 @@ for b in builds:
         logs[b['name']].append(f'{name:78s} {ms:8.3f} ms {4.0*S/ms/1e6:7.0f} GB/s')
         if b is builds[-1]:
             print(logs[b['name']][-1], flush=True)
+# ---- hipdsp_find_peaks: the peaks of the whole envelope above 0.25 with a prominence of at least 0.1 (tools/peaks_bench.py has
+# white noise, the pure scan and hipdsp_region_stats over the same slab)
+for b in builds:
+    h, ctx = b['h'], b['ctx']
+    if not hasattr(h.lib, 'hipdsp_find_peaks'):
+        continue
+    pk, pr, cnt = h.DeviceArray(ctx, (C, 65536), np.int64), h.DeviceArray(ctx, (C, 65536, 4), np.float64), h.DeviceArray(ctx, (C,), np.int64)
+    borders = [0.25, np.inf, -np.inf, np.inf, 0.1, np.inf]
+    ms = min(timed(b, lambda: h.find_peaks_into(ctx, b['buf']['de'], T, C, 0, T, borders, 0, 65536, pk, pr, cnt), 5) for _ in range(rounds))
+    ctx.synchronize()
+    logs[b['name']].append(f'{"hipdsp_find_peaks, the whole envelope, height 0.25, prominence 0.1":78s} {ms:8.3f} ms {4.0*S/ms/1e6:7.0f} GB/s')
+    if b is builds[-1]:
+        print(logs[b['name']][-1], flush=True)
 prefix = os.environ.get('OUT_PREFIX')
 if prefix:
     for name, lines in logs.items():
