@@ -293,3 +293,42 @@ class StatisticsAnalyzer(Analyzer):
             for c in channels:
                 self.store(stats[k, c, 1], stats[k, c, 2])
         return True
+
+
+class PeakFrequencyAnalyzer(Analyzer):
+    """Frequency and power of the main spectral peak of the region of one trace: env_freqs of the reference's
+    songdetector.py (songdetector.py:146-152) as an analyzer -- on the filtered trace the carrier of a call, on an
+    envelope the pulse rate of a song (BufferedArray.peak_freqs: Welch spectrum with a window of rate/freq_resolution
+    samples or the largest power of two the region holds; `thresh` in dB of prominence, None for the largest bin).  The
+    frequency is NaN for a region shorter than min_nfft samples."""
+
+    def __init__(self, graph, source_name='filtered', freq_resolution=10.0, thresh=None, min_nfft=16, max_nfft=8192,
+                 step=1):
+        super().__init__(graph, 'peak frequency', source_name)
+        self.freq_resolution, self.thresh = float(freq_resolution), thresh
+        self.min_nfft, self.max_nfft, self.step = int(min_nfft), int(max_nfft), int(step)
+        us = self.source.unit
+        self.make_column('peak frequency', 'Hz', '%.2f')
+        self.make_column('peak power', f'{us}^2/Hz' if us else '1/Hz', '%.4g')
+
+    def _peaks(self, table):
+        trace = self.source
+        if table:
+            trace.update_buffer(min(a for c, a, b in table), max(b for c, a, b in table))
+        freqs, powers = trace.peak_freqs(table, self.freq_resolution, self.min_nfft, self.max_nfft, self.thresh,
+                                         self.step, powers=True)
+        return freqs, powers
+
+    def analyze(self, t0, t1, channel, traces):
+        i0, i1 = self.graph.region_frames(self.source, t0, t1)
+        freqs, powers = self._peaks([(channel, i0, i1)])
+        self.store(float(freqs[channel][0]), float(powers[channel][0]))
+
+    def analyze_many(self, regions, channels):
+        spans = [self.graph.region_frames(self.source, t0, t1) for t0, t1 in regions]
+        # one device call per nfft for all regions and channels; the rows come back per channel in region order
+        freqs, powers = self._peaks([(c, a, b) for a, b in spans for c in channels])
+        for k in range(len(spans)):
+            for c in channels:
+                self.store(float(freqs[c][k]), float(powers[c][k]))
+        return True

@@ -290,6 +290,89 @@ class BufferedArray(object):
                                    first=self.offset + a) for c in range(self.channels)]
         return Peaks(results, self.rate, getattr(self, 'name', None))
 
+    def _spectra_arguments(self, regions, nfft, hop, step):
+        """((R, 3) int64 table of channel, start, stop relative to the buffer, hop) of a region_spectra call."""
+        from .spectra import MAX_NFFT, MIN_NFFT
+        if len(self.shape) > 2:
+            raise TypeError('region_spectra is for traces, not for spectrogram-shaped data')
+        nfft = int(nfft)
+        if nfft < MIN_NFFT or nfft > MAX_NFFT or nfft & (nfft - 1):
+            raise ValueError('nfft %d is not a power of two in [%d, %d]' % (nfft, MIN_NFFT, MAX_NFFT))
+        hop = nfft//2 if hop is None else int(hop)
+        if hop < 1 or hop > nfft or int(step) < 1:
+            raise ValueError('hop %d not in [1, nfft], or step %d < 1' % (hop, int(step)))
+        tab = np.asarray([(int(c), int(a), int(b)) for c, a, b in regions], dtype=np.int64).reshape(-1, 3)
+        if len(tab) and (tab[:, 0].min() < 0 or tab[:, 0].max() >= self.channels):
+            raise IndexError('channel outside the trace')
+        tab[:, 1:] -= self.offset
+        n = len(self._buf())
+        if len(tab) and (tab[:, 1].min() < 0 or tab[:, 2].max() > n or (tab[:, 2] < tab[:, 1]).any()):
+            raise IndexError('range outside the loaded buffer')
+        return tab, hop
+
+    def region_spectra(self, regions, nfft, hop=None, step=1):
+        """Welch power spectral densities of frames [start, stop) (absolute, inside the current buffer) of one channel
+        for every (channel, start, stop) of `regions`, with numpy on the host buffer: Hann frames of `nfft` every `hop`
+        (nfft//2 by default) of the samples trace[start:stop:step, channel] (float32, as on the device mirror), mean
+        removed per frame, density scaling at rate/step (spectra.py; the definition: hipdsp_region_spectra in
+        include/hip_dsp.h, which is scipy.signal.welch; BufferedData.region_spectra is the same on the device
+        mirror).  `nfft` is a power of two in 8 ... 8192.  TypeError for spectrogram-shaped traces.  Returns a Spectra
+        object."""
+        from .spectra import Spectra, host_region_spectrum
+        tab, hop = self._spectra_arguments(regions, nfft, hop, step)
+        step, fs = int(step), self.rate/int(step)
+        F = int(nfft)//2 + 1
+        power, info = np.zeros((len(tab), F)), np.zeros((len(tab), 2), dtype=np.int64)
+        buf = self.buffer
+        for i, (c, a, b) in enumerate(tab):
+            v = np.asarray(buf[a:b:step, c], dtype=np.float32)
+            power[i], info[i, 0], info[i, 1] = host_region_spectrum(v, int(nfft), hop, fs)
+        tab[:, 1:] += self.offset
+        return Spectra(tab, power, info[:, 0], info[:, 1], nfft, hop, step, fs, getattr(self, 'name', None))
+
+    def _spectra_peaks(self, regions, nfft, hop, step, thresh):
+        """(peak frequencies in Hz, their powers) of the regions' spectra at one nfft: what peak_freqs asks of every
+        group of events (BufferedData answers it on the device mirror)."""
+        sp = self.region_spectra(regions, nfft, hop, step)
+        freqs = sp.peak_freqs(thresh)
+        bins = np.rint(np.nan_to_num(freqs)*sp.nfft/sp.fs).astype(np.int64)
+        powers = np.where(np.isnan(freqs), np.nan, sp.power[np.arange(len(sp)), bins])
+        return freqs, powers.astype(np.float64)
+
+    def peak_freqs(self, events, freq_resolution, min_nfft=16, max_nfft=8192, thresh=None, step=1, powers=False):
+        """The main spectral peak of every event in Hz -- env_freqs of the reference's songdetector.py
+        (songdetector.py:146-152): on an envelope the pulse rate of every song, on a filtered trace the carrier of every
+        call.  `events` is an Events object or a list of (channel, start, stop) in absolute frames inside the current
+        buffer.  Every event gets nfft = min(welch_nfft(rate/step, freq_resolution, min_nfft, max_nfft), the largest
+        power of two <= its length in decimated samples) -- thunderlab's use of max_nfft = i1 - i0, restated -- and a
+        hop of nfft//2; events shorter than min_nfft give NaN.  Events are grouped by nfft (at most ten groups), one
+        region_spectra call per group.  `thresh`: None takes the largest bin, a number the largest peak of at least that
+        prominence in dB (spectra.pick_peak; songdetector.py uses 10).  Returns one float64 array of Hz per channel,
+        aligned with events.onsets[channel] (for a list: in the order given); with powers=True a pair of such lists,
+        the second holding the power at the peak."""
+        from .spectra import event_nfft, welch_nfft
+        step = int(step)
+        if step < 1:
+            raise ValueError('step must be at least 1')
+        if hasattr(events, 'onsets'):
+            table = [(c, int(a), int(b)) for c in range(events.channels)
+                     for a, b in zip(events.onsets[c], events.offsets[c])]
+            channels = events.channels
+        else:
+            table = [(int(c), int(a), int(b)) for c, a, b in events]
+            channels = self.channels
+        top = welch_nfft(self.rate/step, freq_resolution, min_nfft, max_nfft)
+        sizes = np.array([event_nfft(-(-(b - a)//step), top, min_nfft) for c, a, b in table], dtype=np.int64)
+        freqs, power = np.full(len(table), np.nan), np.full(len(table), np.nan)
+        for nfft in sorted(set(sizes.tolist()) - {0}):
+            idx = np.flatnonzero(sizes == nfft)
+            freqs[idx], power[idx] = self._spectra_peaks([table[i] for i in idx], nfft, nfft//2, step, thresh)
+        owner = np.array([c for c, a, b in table], dtype=np.int64)
+        per_channel = [freqs[owner == c] for c in range(channels)]
+        if powers:
+            return per_channel, [power[owner == c] for c in range(channels)]
+        return per_channel
+
     def event_thresholds(self, factor, start=None, stop=None, method='std'):
         """Per-channel thresholds of a detector over frames [start, stop).  method='std': mean + factor*std (the
         alternative songdetector.py:119-127 leaves commented out), from ONE region_stats call over the range.

@@ -604,6 +604,68 @@ class BufferedData(BufferedArray):
         shift = np.array([0.0, 0.0, self.offset, self.offset])
         return Peaks([(pos + self.offset, props + shift) for pos, props in results], self.rate, self.name)
 
+    def _spectra_on_mirror(self, tab):
+        """Can the spectra of the (channel, start, stop) rows of `tab` (relative to the buffer) run on the mirror?"""
+        return len(tab) > 0 and self.channels > 0 and self._dev is not None and \
+            all(_covers(self._dev_valid, a, b) for c, a, b in tab.tolist())
+
+    def region_spectra(self, regions, nfft, hop=None, step=1):
+        """BufferedArray.region_spectra on the device mirror when it is valid over every region (hipdsp_region_spectra:
+        ONE call for all regions, whatever their channels and lengths; only the regions' samples are read and 4*(nfft/2
+        + 1) + 16 bytes per region come back), else numpy on the host buffer.  Nothing is read back from the mirror:
+        the host copy stays as stale as it was.  Returns a Spectra object."""
+        from . import hipdsp
+        from .spectra import Spectra
+        tab, hop = self._spectra_arguments(regions, nfft, hop, step)
+        if not self._spectra_on_mirror(tab):
+            return BufferedArray.region_spectra(self, regions, nfft, hop, step)
+        fs = self.rate/int(step)
+        power, info = hipdsp.region_spectra(self.ctx, self._dev, self._pitch(), self.channels, len(self._hostbuf), tab,
+                                            nfft, hop, int(step), fs)
+        tab[:, 1:] += self.offset
+        return Spectra(tab, power, info[:, 0], info[:, 1], nfft, hop, int(step), fs, self.name)
+
+    def _spectra_peaks(self, regions, nfft, hop, step, thresh):
+        """BufferedArray._spectra_peaks on the device mirror when it is valid over every region: one
+        hipdsp_region_spectra call; without `thresh` only the 16 bytes of info per region and the power of its largest
+        bin come back; with it the rows stay on the device, become dB (hipdsp_decibel with min_power 0: -inf only where
+        the power is exactly 0) and go through hipdsp_find_peaks as the channels of one slab (x_pitch = nfft/2 + 1,
+        prominence >= thresh, at most 65535 rows per call) -- the candidates' positions and heights come back and the
+        host picks the highest of every row (the first of equally high ones)."""
+        from . import hipdsp
+        tab, hop = self._spectra_arguments(regions, nfft, hop, step)
+        if not self._spectra_on_mirror(tab):
+            return BufferedArray._spectra_peaks(self, regions, nfft, hop, step, thresh)
+        R, F, fs = len(tab), int(nfft)//2 + 1, self.rate/int(step)
+        out = hipdsp.DeviceArray(self.ctx, (R, F), np.float32)
+        dinfo = hipdsp.DeviceArray(self.ctx, (R, 2), np.int64)
+        db = None
+        try:
+            hipdsp.region_spectra_into(self.ctx, self._dev, self._pitch(), self.channels, len(self._hostbuf), tab, nfft,
+                                       hop, int(step), fs, out, dinfo)
+            info = dinfo.to_host()
+            bins = np.where(info[:, 0] > 0, info[:, 1], -1)
+            if thresh is not None:
+                db = hipdsp.DeviceArray(self.ctx, (R, F), np.float32)
+                hipdsp.decibel(self.ctx, out, db, R*F, 1.0, 0.0)
+                borders = [-np.inf, np.inf, -np.inf, np.inf, float(thresh), np.inf]
+                for k in range(0, R, 65535):
+                    rows = min(65535, R - k)
+                    found = hipdsp.find_peaks(self.ctx, db.view(k*F, (rows, F)), F, rows, 0, F, borders)
+                    for i, (pos, props) in enumerate(found):
+                        # an all-NaN row (a non-finite sample, or no frame) has no peak
+                        bins[k + i] = pos[np.argmax(props[:, 0])] if len(pos) else -1
+            freqs, powers = np.full(R, np.nan), np.full(R, np.nan)
+            for i in np.flatnonzero(bins >= 0):
+                p = out.view(i*F + int(bins[i]), (1,)).to_host()[0]
+                if not np.isnan(p):
+                    freqs[i], powers[i] = int(bins[i])*fs/int(nfft), float(p)
+            return freqs, powers
+        finally:
+            for d in (out, dinfo, db):
+                if d is not None:
+                    d.free()
+
     def histogram(self, edges, start=None, stop=None, channel=None):
         """BufferedArray.histogram on the device mirror when it is valid over the range (hipdsp_histogram: the trace is
         read once on the device, 8*(B + 3) bytes per channel come back), else numpy on the host buffer.  Nothing is

@@ -596,6 +596,39 @@ def region_stats(ctx, x, x_pitch, channels, frames, regions, out=None):
     return res
 
 
+SPECTRA_GROUP = 16                      # frames per work item of hipdsp_region_spectra (csrc/regionspectra.hip: SP_GROUP)
+
+
+def region_spectra_into(ctx, x, x_pitch, channels, frames, regions, nfft, hop, step, fs, out, info, out_pitch=0):
+    """One hipdsp_region_spectra launch, the results staying on the device: `out` (len(regions), nfft//2 + 1) float32
+    and `info` (len(regions), 2) int64 are DeviceArrays; `regions` is an (n, 3) int64 host table of channel, start,
+    stop."""
+    tab = np.ascontiguousarray(regions, dtype=np.int64).reshape(-1, 3)
+    _count('region_spectra')
+    check(lib.hipdsp_region_spectra(ctx.handle, _p(x), int(x_pitch), int(channels), int(frames),
+                                    tab.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), len(tab), int(nfft), int(hop),
+                                    int(step), float(fs), _p(out), int(out_pitch), _p(info)))
+
+
+def region_spectra(ctx, x, x_pitch, channels, frames, regions, nfft, hop, step, fs):
+    """Welch PSDs of x[channel, start:stop:step] for every (channel, start, stop) of `regions` (hipdsp_region_spectra:
+    Hann frames of `nfft` every `hop` decimated samples, mean removed, density scaling at rate `fs`).  Returns the
+    (len(regions), nfft//2 + 1) float32 rows and the (len(regions), 2) int64 array of n_frames and np.argmax(row)."""
+    tab = np.ascontiguousarray(regions, dtype=np.int64).reshape(-1, 3)
+    n, F = len(tab), int(nfft)//2 + 1
+    if n == 0:
+        region_spectra_into(ctx, x, x_pitch, channels, frames, tab, nfft, hop, step, fs, None, None)
+        return np.zeros((0, F), dtype=np.float32), np.zeros((0, 2), dtype=np.int64)
+    out = DeviceArray(ctx, (n, F), np.float32)
+    info = DeviceArray(ctx, (n, 2), np.int64)
+    try:
+        region_spectra_into(ctx, x, x_pitch, channels, frames, tab, nfft, hop, step, fs, out, info)
+        return out.to_host(), info.to_host()
+    finally:
+        out.free()
+        info.free()
+
+
 def detect_events_into(ctx, x, x_pitch, channels, start, stop, thresholds, min_gap, min_len, capacity, events, counts,
                        events_pitch=0):
     """One hipdsp_detect_events launch, everything staying on the device: `events` (channels, capacity, 2) int64 (None with

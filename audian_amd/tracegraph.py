@@ -194,6 +194,35 @@ class TraceGraph(object):
         i0, i1 = self._event_frames(trace, t0, t1)
         return trace.find_peaks(height, threshold, prominence, wlen, i0, i1)
 
+    def event_peak_freqs(self, events, trace_name=None, freq_resolution=1.0, thresh=None, step=None, min_nfft=16,
+                         max_nfft=8192):
+        """The main spectral peak of every event in Hz -- env_freqs of the reference's songdetector.py
+        (songdetector.py:146-152, called at :761) -- taken on `trace_name` (by default the trace the events were
+        detected on): on an envelope the pulse rate of every song, on the filtered trace the carrier of every call.
+        The buffers are moved as in detect_events so that the trace holds all events, then the trace computes
+        (BufferedData.peak_freqs: on its device mirror when it has one, one call per nfft).  `step` decimates the
+        trace before the spectra; None means 1, except on a BufferedEnvelope, which lives at the full rate here: there
+        it is max(1, round(rate / (10*envelope_cutoff))), the reference's envrate (songdetector.py:63-66).  Returns
+        one array of Hz per channel, aligned with events.onsets[channel]."""
+        from .bufferedenvelope import BufferedEnvelope
+        trace = self[events.trace_name if trace_name is None else trace_name]
+        if step is None:
+            step = 1
+            if isinstance(trace, BufferedEnvelope):
+                step = max(1, int(round(trace.rate/(10.0*trace.envelope_cutoff))))
+        if len(events) > 0:
+            first = min(int(o.min()) for o in events.onsets if len(o))
+            last = max(int(o.max()) for o in events.offsets if len(o))
+            scale = trace.rate/events.rate
+            a, b = int(np.floor(first*scale)), int(np.ceil(last*scale))
+            if a < trace.offset or b > trace.offset + len(trace._buf()):
+                self._event_frames(trace, (first + 0.5)/events.rate, (last - 0.5)/events.rate)   # as Events.regions
+            if scale != 1.0:
+                from .events import Events
+                events = Events([np.stack((np.floor(events.onsets[c]*scale), np.ceil(events.offsets[c]*scale)), axis=1)
+                                 for c in range(events.channels)], trace.rate, trace.name)
+        return trace.peak_freqs(events, freq_resolution, min_nfft, max_nfft, thresh, step)
+
     @staticmethod
     def mark_peaks(analyzer, name, peaks):
         """Fill the analyzer's point events `name` (Analyzer.make_trace_events) with the peaks: (times, heights) of

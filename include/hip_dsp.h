@@ -817,6 +817,63 @@ int hipdsp_histogram(hipdsp_ctx *ctx, const float *x, int64_t x_pitch, int64_t c
 int hipdsp_masked_stats(hipdsp_ctx *ctx, const float *x, int64_t x_pitch, int64_t channels, int64_t start,
                         int64_t stop, const double *dev_bounds, double *out);
 
+/* ---- event spectra ---------------------------------------------------------- */
+
+/* Welch power spectral densities of many regions in one call: the frequency content of detected events, the step that
+ * follows event detection in the reference's songdetector.py (env_freqs, songdetector.py:146-152, called at :761: the
+ * power spectrum of the envelope inside every song and its main peak, the pulse rate; on the filtered trace the same
+ * gives the carrier of every call).  thunderlab, whose psd and peak_freqs songdetector.py calls, is neither in the
+ * reference tree nor in this image: its choice of nfft and its peak detector are restated (audian_amd/spectra.py),
+ * parity with thunderlab is unpinned.  The contract is the definition below; tests/spectra_definition.py restates it
+ * and tests/golden/region_spectra.npz pins it to scipy.signal.welch (scipy 1.15.3).
+ * x is planar float32: `channels` rows of `frames` valid elements, x_pitch elements apart (0 = frames).  host_regions is
+ * a HOST array (n_regions, 3) of int64: channel, start, stop, with 0 <= channel < channels and 0 <= start <= stop <=
+ * frames; regions may overlap or repeat.  nfft is a power of two in [8, 8192], 1 <= hop <= nfft, step >= 1, fs > 0.
+ * Per region, with v = x[channel, start:stop:step] (len(v) = ceil((stop - start) / step)) converted exactly to float64:
+ *   n_frames = (len(v) - nfft) / hop + 1 (rounded down) when len(v) >= nfft, else 0; frame k is v[k*hop : k*hop + nfft];
+ *   the samples behind the last whole frame are not used (and not read).
+ *   Per frame, exactly what hipdsp_spectrogram does per frame: subtract the frame's mean, multiply by the periodic Hann
+ *   window w[i] = 0.5 - 0.5 cos(2 pi i / nfft), take the real transform X, P = |X|^2 / (fs * sum w^2), bins 1 ... F-2
+ *   doubled, F = nfft/2 + 1.
+ *   The region's row is the mean of its frames' P: scipy.signal.welch(v, fs, 'hann', nperseg=nfft, noverlap=nfft - hop,
+ *   detrend='constant', scaling='density').  fs is taken as given (the rate of v, not of x).
+ * out is a DEVICE array (n_regions, F) float32, out_pitch elements between rows (0 = F); info is a DEVICE array
+ * (n_regions, 2) of int64 and receives n_frames and np.argmax(row), the first position of the largest stored value.
+ * Special values:
+ *   n_frames == 0                           a row of NaN, argmax -1.
+ *   a NaN or +-inf in a sample of a frame   the whole row NaN, argmax 0 (numpy's argmax of an all-NaN row); other
+ *                                           regions are not affected, nor is the region by such samples behind its last
+ *                                           whole frame.
+ *   every used frame constant               the row is exactly 0.0 (the mean of equal samples is exact in float64).
+ * HIPDSP_ERR_INVALID: a NULL ctx, an nfft that is not a power of two in [8, 8192], hop outside [1, nfft], step < 1, fs
+ * not positive and finite, negative sizes, x_pitch < frames, out_pitch < F (other than 0), a NULL table or output, a
+ * region with its channel outside [0, channels) or its range outside [0, frames] or with stop < start, misaligned
+ * pointers, more than 2^31 - 1 frame groups in all.  All of this is decided on the host before anything is launched.
+ * n_regions == 0 writes nothing.
+ * The call reads host memory (the table) and uploads it itself, waiting once for the context's stream while the copy
+ * completes: it is NOT legal inside hipdsp_graph_begin/end (HIPDSP_ERR_INVALID there).
+ * Work: a flat list of (region, frame group) items, sized exactly from the table -- a group is 16 consecutive frames of
+ * one region, counted from the region's first frame -- one workgroup per item, so short events launch nothing for long
+ * ones.  Only samples of the listed regions are read, each at most ceil(nfft / hop) times per region that holds it.  A
+ * workgroup transforms its frames one after the other in LDS (a complex radix-2 Stockham transform of nfft/2 points and a
+ * split step, twiddles and window from one float32 table built once per workgroup from float64 values; 12 * nfft bytes
+ * of LDS) and keeps the bins' running sums on chip, in float64: no spectrum of a single frame goes to memory.  The frame
+ * mean is summed and subtracted in float64 before the sample is rounded to float32, so a DC offset of 10^4 times the
+ * signal costs nothing.  A second launch, one workgroup per region, merges the groups' partial rows in ascending order.
+ * Uses the context scratch: 32 * (n_regions + 1) bytes (the table) plus 8 * (F + 1) bytes per frame group (one float64
+ * partial row and the group's flag), sum over the regions of ceil(n_frames / 16) groups -- like hipdsp_region_stats it
+ * may not come between phase 1 and phase 2 of hipdsp_sosfilt_envelope.
+ * Accuracy: every frame's spectrum meets the per-bin bound every spectrogram kernel is held to (tests/spectral_bound.py:
+ * |a^ - a| <= beta_max * eps * (a + log2(nfft) * r) in amplitudes); the row adds the float64 mean and one rounding to
+ * float32.  tests/test_gpu_regionspectra.py holds every bin to the bound that follows.
+ * Determinism: no atomics.  Frame groups are anchored at the region's first frame and sized by a constant, and partial
+ * rows are merged in an order fixed by their count: a region's row and info depend on its samples and on (nfft, hop,
+ * step, fs) only -- not on which other regions ride in the call, on their order, on n_regions or on channels -- and the
+ * same call gives the same bytes twice.  Index arithmetic is 64-bit; rows and regions start at any 4-byte address. */
+int hipdsp_region_spectra(hipdsp_ctx *ctx, const float *x, int64_t x_pitch, int64_t channels, int64_t frames,
+                          const int64_t *host_regions, int64_t n_regions, int nfft, int hop, int64_t step, double fs,
+                          float *out, int64_t out_pitch, int64_t *info);
+
 /* ---- multi-GPU exchange ---------------------------------------- */
 
 /* One process per GPU, channels sharded in contiguous blocks of the planar layout, so

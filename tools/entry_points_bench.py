@@ -207,6 +207,21 @@ for b in builds:
     logs[b['name']].append(f'{"hipdsp_find_peaks, the whole envelope, height 0.25, prominence 0.1":78s} {ms:8.3f} ms {4.0*S/ms/1e6:7.0f} GB/s')
     if b is builds[-1]:
         print(logs[b['name']][-1], flush=True)
+# ---- hipdsp_region_spectra: ten 5 s events per channel of the filtered buffer, Welch 1024 / 512 (tools/region_spectra_bench.py
+# has the decimated envelope and the per-event route through hipdsp_spectrogram + hipdsp_mean_spectrum_db)
+for b in builds:
+    h, ctx = b['h'], b['ctx']
+    if not hasattr(h.lib, 'hipdsp_region_spectra'):
+        continue
+    n5 = min(int(5*rate), T//10)
+    table = np.array([(c, k*(T//10), k*(T//10) + n5) for c in range(C) for k in range(10)], dtype=np.int64)
+    rows, info = h.DeviceArray(ctx, (len(table), 513), np.float32), h.DeviceArray(ctx, (len(table), 2), np.int64)
+    ms = min(timed(b, lambda: h.region_spectra_into(ctx, b['buf']['df'], T, C, T, table, 1024, 512, 1, rate, rows, info), 5)
+             for _ in range(rounds))
+    ctx.synchronize()
+    logs[b['name']].append(f'{"hipdsp_region_spectra, 10 events of 5 s per channel, 1024/512":78s} {ms:8.3f} ms {4.0*len(table)*n5/ms/1e6:7.0f} GB/s')
+    if b is builds[-1]:
+        print(logs[b['name']][-1], flush=True)
 prefix = os.environ.get('OUT_PREFIX')
 if prefix:
     for name, lines in logs.items():
