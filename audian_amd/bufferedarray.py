@@ -339,6 +339,77 @@ class BufferedArray(object):
         powers = np.where(np.isnan(freqs), np.nan, sp.power[np.arange(len(sp)), bins])
         return freqs, powers.astype(np.float64)
 
+    def _region_table(self, regions, what):
+        """(R, 3) int64 table of channel, start, stop relative to the buffer of a region_filtfilt / region_crossings
+        call."""
+        if len(self.shape) > 2:
+            raise TypeError('%s is for traces, not for spectrogram-shaped data' % what)
+        tab = np.asarray([(int(c), int(a), int(b)) for c, a, b in regions], dtype=np.int64).reshape(-1, 3)
+        if len(tab) and (tab[:, 0].min() < 0 or tab[:, 0].max() >= self.channels):
+            raise IndexError('channel outside the trace')
+        tab[:, 1:] -= self.offset
+        n = len(self._buf())
+        if len(tab) and (tab[:, 1].min() < 0 or tab[:, 2].max() > n or (tab[:, 2] < tab[:, 1]).any()):
+            raise IndexError('range outside the loaded buffer')
+        return tab
+
+    def _filtfilt_arguments(self, regions, sos, out):
+        """(table relative to the buffer, sos (R, S, 6)) of a region_filtfilt call, checked as hipdsp_region_filtfilt
+        checks them: ValueError for a bad filter, a region not longer than its padlen, overlapping regions of one
+        channel; NotImplementedError for more than two sections."""
+        from .refine import check_sos, padlen
+        if out is not None and out is not self:
+            raise TypeError('out is None (the filtered regions are returned) or the trace itself (in place)')
+        tab = self._region_table(regions, 'region_filtfilt')
+        sos = check_sos(np.asarray(sos, dtype=np.float64).reshape(len(tab), -1, 6) if len(tab) else np.zeros((0, 1, 6)))
+        if len(tab):
+            pad = padlen(sos)
+            short = np.flatnonzero(tab[:, 2] - tab[:, 1] <= pad)
+            if len(short):
+                raise ValueError('region %d: the length of the input vector x must be greater than padlen, which is %d'
+                                 % (short[0], pad[short[0]]))
+            order = np.lexsort((tab[:, 2], tab[:, 1], tab[:, 0]))
+            p, q = tab[order[:-1]], tab[order[1:]]
+            if np.any((p[:, 0] == q[:, 0]) & (p[:, 2] > q[:, 1])):
+                raise ValueError('regions of one channel overlap')
+        return tab, sos
+
+    def region_filtfilt(self, regions, sos, clamp=False, out=None, max_scratch=2**30):
+        """Zero-phase filtering of frames [start, stop) (absolute, inside the current buffer) of one channel for every
+        (channel, start, stop) of `regions`, each with its own filter sos[r] ((R, S, 6), S 1 or 2):
+        float32(scipy.signal.sosfiltfilt(sos[r], trace[start:stop, channel])) of the float32 samples, negative values
+        set to 0 with `clamp` (refine.host_region_filtfilt in numpy float64 on the host buffer; the definition:
+        hipdsp_region_filtfilt in include/hip_dsp.h; BufferedData.region_filtfilt is the same on the device mirror,
+        where `max_scratch` bounds the scratch of one call).  out=None returns the filtered regions, one float32
+        array each, and leaves the trace as it is; out=self writes them into the trace (regions of one channel must not
+        overlap either way) and returns the trace."""
+        from .refine import host_region_filtfilt
+        tab, sos = self._filtfilt_arguments(regions, sos, out)
+        buf = self.buffer
+        res = [host_region_filtfilt(np.asarray(buf[a:b, c], dtype=np.float32), sos[i], clamp)
+               for i, (c, a, b) in enumerate(tab)]
+        if out is None:
+            return res
+        for (c, a, b), y in zip(tab, res):
+            buf[a:b, c] = y
+        return self
+
+    def region_crossings(self, regions, thresholds):
+        """(R, 8) float64 per (channel, start, stop) of `regions` (absolute frames inside the current buffer) and its
+        own threshold (one value for all, or one per region): n, the number of samples above, the first sample above,
+        one past the last sample above, the largest sample, its first position, 0, 0 -- positions absolute, -1 for
+        none; float32 comparisons (refine.host_region_crossings on the host buffer; the definition:
+        hipdsp_region_crossings; BufferedData.region_crossings is the same on the device mirror)."""
+        from .refine import host_region_crossings
+        tab = self._region_table(regions, 'region_crossings')
+        thr = np.broadcast_to(np.asarray(thresholds, dtype=np.float64), (len(tab),))
+        buf = self.buffer
+        res = np.zeros((len(tab), 8))
+        for i, (c, a, b) in enumerate(tab):
+            res[i] = host_region_crossings(np.asarray(buf[a:b, c], dtype=np.float32), 0, b - a, thr[i])
+            res[i, [2, 3, 5]] += np.where(res[i, [2, 3, 5]] >= 0, a + self.offset, 0)
+        return res
+
     def peak_freqs(self, events, freq_resolution, min_nfft=16, max_nfft=8192, thresh=None, step=1, powers=False):
         """The main spectral peak of every event in Hz -- env_freqs of the reference's songdetector.py
         (songdetector.py:146-152): on an envelope the pulse rate of every song, on a filtered trace the carrier of every

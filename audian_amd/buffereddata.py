@@ -666,6 +666,51 @@ class BufferedData(BufferedArray):
                 if d is not None:
                     d.free()
 
+    def region_filtfilt(self, regions, sos, clamp=False, out=None, max_scratch=2**30):
+        """BufferedArray.region_filtfilt on the device mirror when it is valid over every region
+        (hipdsp_region_filtfilt: all regions of a call in six launches, each with its own filter).  A long table is
+        split, in its order, into calls whose scratch (hipdsp.region_filtfilt_scratch) stays under `max_scratch` bytes
+        -- the same bytes as one call, a region's result does not depend on what rides with it.  out=self filters in
+        place on the mirror and marks the host copy stale there; out=None leaves the trace alone and returns the
+        filtered regions (a device copy of the buffer's shape takes them; only they cross to the host)."""
+        from . import hipdsp
+        tab, sos = self._filtfilt_arguments(regions, sos, out)
+        if not self._spectra_on_mirror(tab):
+            return BufferedArray.region_filtfilt(self, regions, sos, clamp, out, max_scratch)
+        n = len(self._hostbuf)
+        groups, first = [], 0
+        for i in range(1, len(tab) + 1):
+            if i == len(tab) or hipdsp.region_filtfilt_scratch(tab[first:i + 1], sos[first:i + 1]) > max_scratch:
+                groups.append((first, i))
+                first = i
+        if out is self:
+            dev = self._mirror()                        # (a mirror that is a view becomes a real one: it is written)
+            pitch = self._pitch()
+            for a, b in groups:
+                hipdsp.region_filtfilt(self.ctx, dev, pitch, dev, pitch, self.channels, n, tab[a:b], sos[a:b], clamp)
+            self._stale = _merge(list(self._stale) + [[int(a), int(b)] for c, a, b in tab])
+            self.buffer_changed[:] = True
+            return self
+        tmp = hipdsp.DeviceArray(self.ctx, (self.channels, n), np.float32)
+        try:
+            for a, b in groups:
+                hipdsp.region_filtfilt(self.ctx, self._dev, self._pitch(), tmp, n, self.channels, n, tab[a:b], sos[a:b],
+                                       clamp)
+            return [tmp.view(int(c)*n + int(a), (int(b - a),)).to_host() for c, a, b in tab]
+        finally:
+            tmp.free()
+
+    def region_crossings(self, regions, thresholds):
+        """BufferedArray.region_crossings on the device mirror when it is valid over every region: ONE
+        hipdsp_region_crossings call, 64 bytes per region come back.  Nothing is read back from the mirror."""
+        from . import hipdsp
+        tab = self._region_table(regions, 'region_crossings')
+        if not self._spectra_on_mirror(tab):
+            return BufferedArray.region_crossings(self, regions, thresholds)
+        res = hipdsp.region_crossings(self.ctx, self._dev, self._pitch(), self.channels, len(self._hostbuf), tab, thresholds)
+        res[:, [2, 3, 5]] += np.where(res[:, [2, 3, 5]] >= 0, self.offset, 0)
+        return res
+
     def histogram(self, edges, start=None, stop=None, channel=None):
         """BufferedArray.histogram on the device mirror when it is valid over the range (hipdsp_histogram: the trace is
         read once on the device, 8*(B + 3) bytes per channel come back), else numpy on the host buffer.  Nothing is

@@ -629,6 +629,61 @@ def region_spectra(ctx, x, x_pitch, channels, frames, regions, nfft, hop, step, 
         info.free()
 
 
+FILTER_CHUNK = 64                       # samples per hand-over of hipdsp_region_filtfilt (csrc/regionfilter.hip: RF_CHUNK),
+#                                         anchored at the first sample of a region's extended sequence
+FILTER_TILE = 64*FILTER_CHUNK           # samples per wave of it: 64 consecutive chunks staged together
+CROSSINGS_CHUNK = 4096                  # samples per chunk of hipdsp_region_crossings (RC_CHUNK), anchored at the region's start
+
+
+def region_filtfilt_scratch(regions, sos):
+    """Bytes of context scratch one hipdsp_region_filtfilt call over these regions takes (the formula of
+    include/hip_dsp.h)."""
+    from .refine import padlen
+    tab = np.asarray(regions, dtype=np.int64).reshape(-1, 3)
+    sos = np.asarray(sos, dtype=np.float64).reshape(len(tab), -1, 6)
+    ext = tab[:, 2] - tab[:, 1] + 2*padlen(sos)
+    return int(1072*(len(tab) + 1) + 8*len(tab) + 8*ext.sum() +
+               16*sos.shape[1]*(((ext + FILTER_CHUNK - 1)//FILTER_CHUNK).sum() + ((ext + FILTER_TILE - 1)//FILTER_TILE).sum()))
+
+
+def region_filtfilt(ctx, x, x_pitch, y, y_pitch, channels, frames, regions, sos, clamp=False):
+    """y[channel, start:stop] = float32(scipy.signal.sosfiltfilt(sos_r, x[channel, start:stop])) for every (channel,
+    start, stop) of `regions` ((R, 3) int64, host) with the region's own filter sos[r] ((R, S, 6) float64, S 1 or 2), in
+    one hipdsp_region_filtfilt call; nothing else of y is written; y may be x (with equal pitches)."""
+    tab = np.ascontiguousarray(regions, dtype=np.int64).reshape(-1, 3)
+    sos = np.ascontiguousarray(sos, dtype=np.float64)
+    if sos.ndim != 3 or sos.shape[0] != len(tab) or sos.shape[2] != 6:
+        raise ValueError('sos must be (len(regions), n_sections, 6), got %r' % (sos.shape,))
+    _count('region_filtfilt')
+    check(lib.hipdsp_region_filtfilt(ctx.handle, _p(x), int(x_pitch), _p(y), int(y_pitch), int(channels), int(frames),
+                                     tab.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), len(tab),
+                                     sos.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(sos.shape[1]),
+                                     int(bool(clamp))))
+
+
+def region_crossings(ctx, x, x_pitch, channels, frames, regions, thresholds, out=None):
+    """n, number above, first above, one past the last above, max, argmax, 0, 0 of x[channel, start:stop] for every
+    (channel, start, stop) of `regions` against the region's own threshold (hipdsp_region_crossings; positions in the
+    row, -1 for none).  Returns the (len(regions), 8) float64 host array, or fills `out` (a DeviceArray of that shape)
+    and returns it without any copy."""
+    tab = np.ascontiguousarray(regions, dtype=np.int64).reshape(-1, 3)
+    thr = np.ascontiguousarray(np.broadcast_to(np.asarray(thresholds, dtype=np.float64), (len(tab),)))
+    if len(thr) == 0:
+        thr = np.zeros(1)
+    dev = out if out is not None else (DeviceArray(ctx, (len(tab), 8), np.float64) if len(tab) else None)
+    _count('region_crossings')
+    try:
+        check(lib.hipdsp_region_crossings(ctx.handle, _p(x), int(x_pitch), int(channels), int(frames),
+                                          tab.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                          thr.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), len(tab), _p(dev)))
+        if out is not None:
+            return out
+        return dev.to_host() if dev is not None else np.zeros((0, 8))
+    finally:
+        if out is None and dev is not None:
+            dev.free()
+
+
 def detect_events_into(ctx, x, x_pitch, channels, start, stop, thresholds, min_gap, min_len, capacity, events, counts,
                        events_pitch=0):
     """One hipdsp_detect_events launch, everything staying on the device: `events` (channels, capacity, 2) int64 (None with

@@ -223,6 +223,62 @@ class TraceGraph(object):
                                  for c in range(events.channels)], trace.rate, trace.name)
         return trace.peak_freqs(events, freq_resolution, min_nfft, max_nfft, thresh, step)
 
+    def clean_event_freqs(self, events, freqs, fac=6.0):
+        """clean_env_freqs of the reference's songdetector.py (songdetector.py:155-175, called at :763): frequencies
+        further than fac standard deviations from the mean of the pooled frequencies' middle half become NaN, and
+        events without a frequency are dropped (refine.clean_event_freqs).  Returns (Events, frequencies per
+        channel)."""
+        from .refine import clean_event_freqs
+        return clean_event_freqs(events, freqs, fac)
+
+    def refine_events(self, events, freqs, thresholds, trace_name=None, min_duration=0.1, min_thresh_fac=1.0):
+        """analyse_songs of the reference's songdetector.py (songdetector.py:195-244, called at :767) on `trace_name`
+        (by default the trace the events were detected on; the reference takes the envelope that filter_envelopes
+        smoothed -- a BufferedEventFilter here): around every event a local threshold, 1.2 times the largest sample
+        of the noise windows beside it but at least min_thresh_fac * the channel's threshold, and the event's borders
+        again as the first and last sample above it inside the event widened by int(min_duration * rate) frames;
+        events without a frequency, or with nothing above, are dropped (refine.py has the bookkeeping and the two
+        deviations from the reference).  The buffers are moved as in event_peak_freqs so that the trace holds all
+        windows; then ONE region_crossings call with NaN thresholds over all noise windows brings their maxima, two
+        floats per event, the thresholds are computed on the host, and ONE region_crossings call over the widened
+        events brings the borders.  `thresholds`: one value, or one per channel.  Returns an Events object."""
+        from .events import Events
+        from .refine import local_thresholds, noise_windows
+        trace = self[events.trace_name if trace_name is None else trace_name]
+        thr = np.broadcast_to(np.asarray(thresholds, dtype=np.float64), (events.channels,))
+        scale = trace.rate/events.rate
+        pairs = [events.frames(c) if scale == 1.0 else
+                 np.stack((np.floor(events.onsets[c]*scale), np.ceil(events.offsets[c]*scale)), axis=1).astype(np.int64)
+                 for c in range(events.channels)]
+        w = int(min_duration*trace.rate)
+        n = len(trace)
+        windows = [noise_windows(pairs[c], freqs[c], w, n) for c in range(events.channels)]
+        noise, wide = [], []
+        for c, (wd, before, after) in enumerate(windows):
+            for a, b in np.concatenate((before, after)):
+                noise.append((c, int(a), int(max(a, b))))
+            wide.extend((c, int(a), int(max(a, b))) for a, b in wd)
+        if not wide:
+            return Events([np.zeros((0, 2)) for c in range(events.channels)], trace.rate, trace.name)
+        first, last = min(r[1] for r in noise + wide), max(r[2] for r in noise + wide)
+        if first < trace.offset or last > trace.offset + len(trace._buf()):
+            self._event_frames(trace, (first + 0.5)/trace.rate, (last - 0.5)/trace.rate)
+        maxima = trace.region_crossings(noise, np.nan)[:, 4]
+        local, k = [], 0
+        for c, (wd, before, after) in enumerate(windows):
+            K = len(wd)
+            local.append(local_thresholds(before, after, maxima[k:k + K], maxima[k + K:k + 2*K], freqs[c], float(thr[c]), w,
+                                          min_thresh_fac))
+            k += 2*K
+        found = trace.region_crossings(wide, np.concatenate(local))
+        out, k = [], 0
+        for c, (wd, before, after) in enumerate(windows):
+            rows = found[k:k + len(wd)]
+            k += len(wd)
+            keep = rows[:, 2] >= 0
+            out.append(rows[keep][:, 2:4].astype(np.int64))
+        return Events(out, trace.rate, trace.name)
+
     @staticmethod
     def mark_peaks(analyzer, name, peaks):
         """Fill the analyzer's point events `name` (Analyzer.make_trace_events) with the peaks: (times, heights) of

@@ -874,6 +874,90 @@ int hipdsp_region_spectra(hipdsp_ctx *ctx, const float *x, int64_t x_pitch, int6
                           const int64_t *host_regions, int64_t n_regions, int nfft, int hop, int64_t step, double fs,
                           float *out, int64_t out_pitch, int64_t *info);
 
+/* ---- event refinement ------------------------------------------------------- */
+
+/* Zero-phase filtering of many regions in one call, every region with a filter of its own: the step behind the pulse
+ * rates in the reference's songdetector.py (filter_envelopes, songdetector.py:178-192, called at :765: the envelope
+ * inside every widened song is smoothed by lowpass_filter -- scipy.signal.filtfilt(*butter(1, Wn), v) -- at four times
+ * that song's own pulse rate, in place).
+ * x and y are planar float32: `channels` rows of `frames` valid elements, x_pitch / y_pitch elements apart (0 = frames).
+ * host_regions is a HOST array (n_regions, 3) of int64: channel, start, stop, with 0 <= channel < channels and 0 <=
+ * start <= stop <= frames.  host_sos is a HOST array (n_regions, n_sections, 6) of float64 rows [b0 b1 b2 1 a1 a2]:
+ * region r is filtered with host_sos[r]; n_sections is shared by the call and is 1 or 2.
+ * Per region, with v = x[channel, start:stop] converted exactly to float64:
+ *   y[channel, start:stop] = float32(scipy.signal.sosfiltfilt(sos_r, v))       default padtype 'odd', default padlen
+ * that is: padlen = 3 * (2 n_sections + 1 - min(#sections with b2 == 0, #sections with a2 == 0)); the odd extension
+ * 2 v[0] - v[padlen:0:-1] | v | 2 v[-1] - v[-2:-padlen-2:-1]; a forward pass from sosfilt_zi * ext[0]; reversal; a
+ * forward pass from sosfilt_zi * (its first sample); reversal; the extension trimmed.  tests/iir_bound.py restates it
+ * (sosfiltfilt with gain 1, no rectification, no clamp).  For the reference's filter, butter(1, Wn) as ONE section with
+ * b2 = a2 = 0 (padlen 6), this is scipy.signal.filtfilt(b, a, v); tests/golden/region_filtfilt.npz pins both to scipy
+ * 1.15.3.  With clamp != 0 negative results become 0.  No other element of y is written.
+ * y == x with equal pitches is legal (the reference filters in place): x is read by the forward pass only, which is
+ * complete before the backward pass writes.  Otherwise x and y must not overlap.
+ * Errors, all decided on the host before anything is launched or written:
+ *   HIPDSP_ERR_TOO_SHORT    a region with stop - start <= padlen(sos_r) (scipy raises ValueError).
+ *   HIPDSP_ERR_INVALID      a NULL argument; a0 != 1; a coefficient that is not finite; a section whose poles are not
+ *                           inside the unit circle (|a2| < 1 and |a1| < 1 + a2 fail); a region outside [0, frames] or with
+ *                           stop < start; a channel outside [0, channels); two regions of one channel that overlap (two
+ *                           writers; stop == next start is fine); pitches below frames; misaligned pointers; x and y
+ *                           that overlap other than y == x with equal pitches; a call inside hipdsp_graph_begin/end (the
+ *                           call reads the host tables and uploads them itself, waiting once for the context's stream,
+ *                           like hipdsp_region_spectra).
+ *   HIPDSP_ERR_UNSUPPORTED  n_sections outside 1 ... 2.
+ * n_regions == 0 writes nothing.
+ * Non-finite samples: a region that holds a NaN or +-inf sample comes out all NaN; other regions are not affected.
+ * (scipy gives NaN or infinities there, depending on the filter: an infinity times a zero coefficient, or the difference
+ * of two infinities, is what decides.)
+ * Accuracy: float64 coefficients and state, ONE rounding to float32.  The extension is formed in float64 from the
+ * exactly converted samples and the forward pass reaches the backward pass as float64, so the contract is the one of
+ * tests/iir_bound.py without its extension_term and between_term: e_w <= (1 + 16 q) 2^-24 r_w for every window of 64
+ * samples counted from the region's own start, q the case's allowance.  A region's history starts at its own extension:
+ * there is no warm-up.  Where the extended sequence is cut into chunks the state is handed over exactly, state_out =
+ * A^L state_in + (the zero-state end state of the L samples), in float64 -- over a chunk, over the 1, 2, 4 ... 32 chunks
+ * of a scan over a tile's lanes, and over a tile; the powers of A are computed on the host (squared in long double,
+ * each rounded once).
+ * Work: the extended sequence of a region (E = stop - start + 2 padlen samples) is cut into chunks of 64 samples
+ * counted from its first sample -- for the backward pass from its last -- and 64 consecutive chunks are the tile of one
+ * wave; the flat list of (region, tile) items is sized exactly from the table.  Per direction three launches: every
+ * chunk's zero-state end state (one lane per chunk, the tile staged in LDS with coalesced loads) and a scan of them over
+ * the tile's lanes; one thread per region walking the tiles' hand-overs; every chunk again from its true state, writing.
+ * Uses the context scratch: 1072 * (n_regions + 1) + 8 * n_regions bytes (the table and one flag per region) plus, summed
+ * over the regions, 8 * E bytes (the forward pass, float64) and 16 * n_sections * (ceil(E / 64) + ceil(E / 4096)) bytes
+ * (the states of the chunks and of the tiles) -- like hipdsp_region_stats it may not come between phase 1 and phase 2 of hipdsp_sosfilt_envelope.
+ * Determinism: no atomics.  The chunk grid is anchored at the first (last) sample of the region's extended sequence and
+ * sized by a constant: a region's output depends on its samples, its filter and clamp only -- not on which other regions
+ * ride in the call, on their order, on n_regions or on channels -- and the same call gives the same bytes twice.  Index
+ * arithmetic is 64-bit; rows and regions start at any 4-byte address. */
+int hipdsp_region_filtfilt(hipdsp_ctx *ctx, const float *x, int64_t x_pitch, float *y, int64_t y_pitch,
+                           int64_t channels, int64_t frames, const int64_t *host_regions, int64_t n_regions,
+                           const double *host_sos, int n_sections, int clamp);
+
+/* Threshold crossings and the maximum of many regions in one call, one threshold per REGION: the device step of the
+ * reference's analyse_songs (songdetector.py:195-244, called at :767): the largest envelope value in the noise windows
+ * beside every song gives a local threshold, and the song's borders are found again as the first and last sample above
+ * it inside the widened song.
+ * x and host_regions are as in hipdsp_region_filtfilt; regions may overlap or repeat.  host_thresholds is a HOST array
+ * of n_regions float64.  out is a DEVICE array (n_regions, 8) of float64, compact.  For v = x[channel, start:stop]:
+ *   [0] n = stop - start    [1] number of samples above      [2] position of the first sample above, -1 if none
+ *   [3] one past the position of the last sample above, -1   [4] np.max(v)     [5] np.argmax(v) as a position in the row
+ *   [6], [7] 0 (reserved)
+ * "Above" is rule 1 of hipdsp_detect_events: x[i] > (float)threshold as a float32 comparison; NaN is not above, a
+ * sample equal to the threshold is not above, nothing is above a NaN or +inf threshold -- so a call with NaN
+ * thresholds gives the maxima alone.  Positions are positions in the row, as in hipdsp_detect_events.  [4] and [5]
+ * follow hipdsp_region_stats: a NaN in the region gives NaN and the first NaN's position, n == 0 gives NaN and -1,
+ * otherwise the first occurrence of the largest value.  Everything is exact.
+ * HIPDSP_ERR_INVALID: a NULL argument, negative sizes, x_pitch < frames, a region outside [0, frames] or with stop <
+ * start, a channel outside [0, channels), misaligned pointers, a call inside hipdsp_graph_begin/end (the call reads the
+ * host tables and uploads them itself, waiting once for the context's stream); all decided on the host before anything
+ * is launched.  n_regions == 0 writes nothing.
+ * Work: one workgroup per chunk of 4096 samples counted from the region's start, then one thread per region merging its
+ * chunks in ascending order.  Uses the context scratch: 40 * (n_regions + 1) bytes (the table) plus 24 bytes per chunk,
+ * sum over the regions of ceil(n / 4096) chunks, under the same rule as above.
+ * Determinism: no atomics; a region's eight values depend on its samples and its threshold only, and the same call
+ * gives the same bytes twice. */
+int hipdsp_region_crossings(hipdsp_ctx *ctx, const float *x, int64_t x_pitch, int64_t channels, int64_t frames,
+                            const int64_t *host_regions, const double *host_thresholds, int64_t n_regions, double *out);
+
 /* ---- multi-GPU exchange ---------------------------------------- */
 
 /* One process per GPU, channels sharded in contiguous blocks of the planar layout, so

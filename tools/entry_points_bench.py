@@ -222,6 +222,28 @@ for b in builds:
     logs[b['name']].append(f'{"hipdsp_region_spectra, 10 events of 5 s per channel, 1024/512":78s} {ms:8.3f} ms {4.0*len(table)*n5/ms/1e6:7.0f} GB/s')
     if b is builds[-1]:
         print(logs[b['name']][-1], flush=True)
+# ---- hipdsp_region_filtfilt / hipdsp_region_crossings: the same ten events per channel widened by 1 s on both sides (7 s
+# regions of the envelope), every region with a first-order low-pass of its own, 40 ... 400 Hz (tools/region_filter_bench.py
+# has the per-event routes they replace)
+for b in builds:
+    h, ctx = b['h'], b['ctx']
+    if not hasattr(h.lib, 'hipdsp_region_filtfilt'):
+        continue
+    n7 = min(int(7*rate), T//10)
+    table = np.array([(c, k*(T//10), k*(T//10) + n7) for c in range(C) for k in range(10)], dtype=np.int64)
+    sos = np.array([b['design'].butter_sos(1, f, 'lowpass', rate) for f in np.linspace(40.0, 400.0, len(table))])
+    ms = min(timed(b, lambda: h.region_filtfilt(ctx, b['buf']['de'], T, b['buf']['ds'], T, C, T, table, sos), 3)
+             for _ in range(rounds))
+    ctx.synchronize()
+    logs[b['name']].append(f'{"hipdsp_region_filtfilt, 10 regions of 7 s per channel, order 1":78s} {ms:8.3f} ms {8.0*len(table)*n7/ms/1e6:7.0f} GB/s')
+    if b is builds[-1]:
+        print(logs[b['name']][-1], flush=True)
+    out = h.DeviceArray(ctx, (len(table), 8), np.float64)
+    ms = min(timed(b, lambda: h.region_crossings(ctx, b['buf']['de'], T, C, T, table, 0.5, out=out), 5) for _ in range(rounds))
+    ctx.synchronize()
+    logs[b['name']].append(f'{"hipdsp_region_crossings, 10 regions of 7 s per channel":78s} {ms:8.3f} ms {4.0*len(table)*n7/ms/1e6:7.0f} GB/s')
+    if b is builds[-1]:
+        print(logs[b['name']][-1], flush=True)
 prefix = os.environ.get('OUT_PREFIX')
 if prefix:
     for name, lines in logs.items():
