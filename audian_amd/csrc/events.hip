@@ -19,8 +19,8 @@
 //                     x > thr is the chunk's i-th word of `above` bits, lane i keeps it.  64 words per chunk go to the
 //                     scratch, with the first and last above position of the chunk (absolute, or none).
 //   ev_carry_kernel   one workgroup per channel: exclusive prefix maximum of the last positions and exclusive suffix
-//                     minimum of the first ones along the chunks, in place (the shape of unwrap_scan_kernel: a thread
-//                     owns a contiguous span of chunks, thread 0 joins the 256 spans).
+//                     minimum of the first ones along the chunks, in place (hd_scan_exclusive, rowpass.h: a thread owns
+//                     a contiguous span of chunks, thread 0 joins the 256 spans).
 //   ev_count_kernel   from the bits and the two carried positions: the chunk's onsets and last samples, each last
 //                     sample paired with the nearest onset at or before it; events whose pair lies in the chunk are
 //                     counted if long enough.  The one event that can end in a chunk and begin before it is left
@@ -37,8 +37,7 @@
 //
 // Traffic per sample and channel: 4 B read once, 1/8 B of bits written and 2/8 B read, 40 B of carries per chunk of
 // 4096 samples: about 4.4 B where three passes over the trace would move 12.  Index arithmetic on the array is 64-bit.
-#include "common.h"
-#include <cmath>
+#include "rowpass.h"
 
 namespace {
 
@@ -46,8 +45,6 @@ constexpr int EV_WORDS = 64;                            // 64-bit words of `abov
 constexpr int EV_CHUNK = EV_WORDS * 64;                 // samples per chunk
 constexpr int EV_SCAN_THREADS = 256;
 constexpr long long EV_NONE_AFTER = 0x3fffffffffffffffLL;   // "no above sample after": further than any gap
-constexpr long long EV_MAX_FRAMES = 1LL << 40;          // stop - start of one call
-constexpr long long EV_MAX_CHANNELS = 65535;            // grid.y
 
 typedef unsigned long long u64;
 
@@ -58,27 +55,19 @@ struct EvWork {                                         // the scratch of one ca
     long long *onset;                                   // last onset of the chunk -> of everything before it
     long long *pending;                                 // last sample of the event that ends here and began earlier, -1
     long long *slot;                                    // events counted in the chunk -> the chunk's first output slot
+
+    size_t carve(void *block, size_t per)               // the arrays of `per` (channel, chunk) pairs over `block`: their bytes
+    {
+        HdCarve c(block);
+        bits = c.take<u64>(per * EV_WORDS);
+        before = c.take<long long>(per);
+        after = c.take<long long>(per);
+        onset = c.take<long long>(per);
+        pending = c.take<long long>(per);
+        slot = c.take<long long>(per);
+        return c.bytes();
+    }
 };
-
-__device__ __forceinline__ long long ev_wave_max(long long v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const long long o = __shfl_xor(v, d, 64);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
-__device__ __forceinline__ long long ev_wave_min(long long v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const long long o = __shfl_xor(v, d, 64);
-        v = o < v ? o : v;
-    }
-    return v;
-}
 
 __global__ __launch_bounds__(64) void ev_bits_kernel(const float *__restrict__ x, long long pitch, long long start,
                                                      long long stop, const float *__restrict__ thresholds, float threshold,
@@ -106,8 +95,8 @@ __global__ __launch_bounds__(64) void ev_bits_kernel(const float *__restrict__ x
     const long long at = (c * n_chunks + j) * EV_WORDS + lane;
     w.bits[at] = word;
     const long long p0 = base + (long long)lane * 64;
-    const long long first = ev_wave_min(word ? p0 + __ffsll((long long)word) - 1 : EV_NONE_AFTER);
-    const long long last = ev_wave_max(word ? p0 + 63 - __clzll((long long)word) : -1);
+    const long long first = hd_wave_min(word ? p0 + __ffsll((long long)word) - 1 : EV_NONE_AFTER);
+    const long long last = hd_wave_max(word ? p0 + 63 - __clzll((long long)word) : -1);
     if (lane == 0) {
         w.after[c * n_chunks + j] = first;
         w.before[c * n_chunks + j] = last;
@@ -119,45 +108,9 @@ __global__ __launch_bounds__(EV_SCAN_THREADS) void ev_carry_kernel(long long n_c
 {
     __shared__ long long sh_b[EV_SCAN_THREADS], sh_a[EV_SCAN_THREADS];
     const int t = threadIdx.x;
-    long long *before = w.before + (long long)blockIdx.x * n_chunks;
-    long long *after = w.after + (long long)blockIdx.x * n_chunks;
-    const long long per = (n_chunks + EV_SCAN_THREADS - 1) / EV_SCAN_THREADS;
-    const long long a = per * t < n_chunks ? per * t : n_chunks, b = a + per < n_chunks ? a + per : n_chunks;
-    long long mb = -1, ma = EV_NONE_AFTER;
-    for (long long i = a; i < b; i++) {
-        mb = before[i] > mb ? before[i] : mb;
-        ma = after[i] < ma ? after[i] : ma;
-    }
-    sh_b[t] = mb;
-    sh_a[t] = ma;
-    __syncthreads();
-    if (t == 0) {
-        long long run = -1;
-        for (int k = 0; k < EV_SCAN_THREADS; k++) {
-            const long long v = sh_b[k];
-            sh_b[k] = run;
-            run = v > run ? v : run;
-        }
-        run = EV_NONE_AFTER;
-        for (int k = EV_SCAN_THREADS - 1; k >= 0; k--) {
-            const long long v = sh_a[k];
-            sh_a[k] = run;
-            run = v < run ? v : run;
-        }
-    }
-    __syncthreads();
-    long long run = sh_b[t];
-    for (long long i = a; i < b; i++) {
-        const long long v = before[i];
-        before[i] = run;
-        run = v > run ? v : run;
-    }
-    run = sh_a[t];
-    for (long long i = b - 1; i >= a; i--) {
-        const long long v = after[i];
-        after[i] = run;
-        run = v < run ? v : run;
-    }
+    hd_scan_exclusive<EV_SCAN_THREADS, false>(w.before + (long long)blockIdx.x * n_chunks, n_chunks, sh_b, t, -1, HdMaxOp());
+    hd_scan_exclusive<EV_SCAN_THREADS, true>(w.after + (long long)blockIdx.x * n_chunks, n_chunks, sh_a, t, EV_NONE_AFTER,
+                                             HdMinOp());
 }
 
 // What a lane knows of its word (samples p0 .. p0 + 63 of the row) once the neighbours are in: the onsets and the last
@@ -242,8 +195,8 @@ __global__ __launch_bounds__(64) void ev_count_kernel(long long start, long long
     }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) kept += __shfl_xor(kept, d, 64);
-    pending = ev_wave_max(pending);                     // at most one lane has one
-    const long long last_on = ev_wave_max(l.on ? l.p0 + 63 - __clzll((long long)l.on) : -1);
+    pending = hd_wave_max(pending);                     // at most one lane has one
+    const long long last_on = hd_wave_max(l.on ? l.p0 + 63 - __clzll((long long)l.on) : -1);
     if (lane == 0) {
         w.slot[c * n_chunks + j] = kept;
         w.pending[c * n_chunks + j] = pending;
@@ -262,23 +215,11 @@ __global__ __launch_bounds__(EV_SCAN_THREADS) void ev_slots_kernel(long long n_c
     long long *onset = w.onset + (long long)blockIdx.x * n_chunks;
     long long *slot = w.slot + (long long)blockIdx.x * n_chunks;
     const long long *pending = w.pending + (long long)blockIdx.x * n_chunks;
-    const long long per = (n_chunks + EV_SCAN_THREADS - 1) / EV_SCAN_THREADS;
-    const long long a = per * t < n_chunks ? per * t : n_chunks, b = a + per < n_chunks ? a + per : n_chunks;
+    const HdSlice s = hd_slice<EV_SCAN_THREADS>(n_chunks, t);
     long long m = -1;
-    for (long long i = a; i < b; i++) m = onset[i] > m ? onset[i] : m;
-    sh[t] = m;
-    __syncthreads();
-    if (t == 0) {
-        long long run = -1;
-        for (int k = 0; k < EV_SCAN_THREADS; k++) {
-            const long long v = sh[k];
-            sh[k] = run;
-            run = v > run ? v : run;
-        }
-    }
-    __syncthreads();
-    long long run = sh[t], sum = 0;
-    for (long long i = a; i < b; i++) {
+    for (long long i = s.a; i < s.b; i++) m = onset[i] > m ? onset[i] : m;
+    long long run = hd_scan_carry<EV_SCAN_THREADS, false>(sh, t, m, -1, HdMaxOp()), sum = 0;
+    for (long long i = s.a; i < s.b; i++) {
         const long long v = onset[i], p = pending[i];
         onset[i] = run;
         // a pending event has its onset in an earlier chunk (onsets and last samples alternate): run >= 0 then
@@ -286,21 +227,9 @@ __global__ __launch_bounds__(EV_SCAN_THREADS) void ev_slots_kernel(long long n_c
         sum += slot[i];
         run = v > run ? v : run;
     }
-    __syncthreads();
-    sh[t] = sum;
-    __syncthreads();
-    if (t == 0) {
-        long long acc = 0;
-        for (int k = 0; k < EV_SCAN_THREADS; k++) {
-            const long long v = sh[k];
-            sh[k] = acc;
-            acc += v;
-        }
-        sh_total = acc;
-    }
-    __syncthreads();
-    run = sh[t];
-    for (long long i = a; i < b; i++) {
+    __syncthreads();                                    // every thread has its onset carry out of sh
+    run = hd_scan_carry<EV_SCAN_THREADS, false>(sh, t, sum, 0, HdSumOp(), &sh_total);
+    for (long long i = s.a; i < s.b; i++) {
         const long long v = slot[i];
         slot[i] = run;
         run += v;
@@ -322,13 +251,7 @@ __global__ __launch_bounds__(64) void ev_emit_kernel(long long start, long long 
         const long long on = ev_onset_of(l, b);
         if (on >= 0 && l.p0 + b + 1 - on >= min_len) kept++;
     }
-    int incl = kept;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += o;
-    }
-    long long at = w.slot[cj] + (incl - kept);
+    long long at = w.slot[cj] + hd_wave_exclusive(kept, lane);
     long long *out = events + c * events_pitch;
     for (u64 m = l.end; m; m &= m - 1) {
         const int b = __ffsll((long long)m) - 1;
@@ -350,21 +273,12 @@ extern "C" int hipdsp_detect_events(hipdsp_ctx *ctx, const float *x, int64_t x_p
                                     int64_t min_len, int64_t capacity, int64_t *events, int64_t events_pitch,
                                     int64_t *counts)
 {
-    HD_REQUIRE(ctx != nullptr, "ctx is NULL");
-    HD_REQUIRE(channels >= 0, "negative number of channels");
-    HD_REQUIRE(start >= 0 && start <= stop, "elements [%lld, %lld) are no range", (long long)start, (long long)stop);
+    HD_TRY(hd_check_rows(ctx, channels, start, stop));
     HD_REQUIRE(min_gap >= 0 && min_len >= 0, "negative min_gap or min_len");
     HD_REQUIRE(capacity >= 0, "negative capacity");
     if (events_pitch == 0) events_pitch = 2 * capacity;
     HD_REQUIRE(events_pitch >= 2 * capacity, "events_pitch smaller than 2*capacity");
-    if (channels > EV_MAX_CHANNELS) {
-        hipdsp_set_error("at most %lld channels per call, got %lld", EV_MAX_CHANNELS, (long long)channels);
-        return HIPDSP_ERR_UNSUPPORTED;
-    }
-    if (stop - start > EV_MAX_FRAMES) {
-        hipdsp_set_error("at most 2^40 elements per row and call, got %lld", (long long)(stop - start));
-        return HIPDSP_ERR_UNSUPPORTED;
-    }
+    HD_TRY(hd_check_rows_limits(channels, stop - start, HD_MAX_FRAMES));
     if (channels == 0) return HIPDSP_OK;
     HD_REQUIRE(counts != nullptr, "counts is NULL");
     HD_REQUIRE(events != nullptr || capacity == 0, "events is NULL with a capacity of %lld", (long long)capacity);
@@ -374,21 +288,13 @@ extern "C" int hipdsp_detect_events(hipdsp_ctx *ctx, const float *x, int64_t x_p
         HD_CHECK_HIP(hipMemsetAsync(counts, 0, sizeof(int64_t) * (size_t)channels, ctx->stream));
         return HIPDSP_OK;
     }
-    HD_REQUIRE(x != nullptr, "NULL data pointer");
-    HD_REQUIRE(((uintptr_t)x & 3) == 0, "x is not aligned to 4 bytes");
-    HD_REQUIRE(x_pitch >= stop || channels == 1, "x_pitch smaller than stop");
+    HD_TRY(hd_check_rows_x(x, x_pitch, channels, start, stop));
     const long long n_chunks = (stop - start + EV_CHUNK - 1) / EV_CHUNK;
     const size_t per = (size_t)n_chunks * (size_t)channels;
-    void *work = nullptr;
-    int rc = hipdsp_scratch(ctx, per * (EV_WORDS + 5) * 8, &work);
-    if (rc != HIPDSP_OK) return rc;
     EvWork w;
-    w.bits = (u64 *)work;
-    w.before = (long long *)(w.bits + per * EV_WORDS);
-    w.after = w.before + per;
-    w.onset = w.after + per;
-    w.pending = w.onset + per;
-    w.slot = w.pending + per;
+    void *work = nullptr;
+    HD_TRY(hipdsp_scratch(ctx, w.carve(nullptr, per), &work));
+    w.carve(work, per);
     const dim3 grid((unsigned)n_chunks, (unsigned)channels);
     hipLaunchKernelGGL(ev_bits_kernel, grid, dim3(64), 0, ctx->stream, x, (long long)x_pitch, (long long)start,
                        (long long)stop, dev_thresholds, (float)threshold, n_chunks, w);

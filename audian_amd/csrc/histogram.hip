@@ -6,9 +6,8 @@
 //
 // Both read the trace once, on the chunk grid of regionstats.hip: one workgroup of 256 threads per (chunk, channel), the
 // grid anchored at `start`, HG_CHUNK = 16384 elements per chunk (the last one fewer).  A thread holds its 64 samples of
-// the chunk in registers (sixteen 16-byte loads, all issued before the first use; the up to three samples before the
-// first 16-byte boundary and after the last whole vector are loaded one by one).  What a chunk computes depends on
-// nothing but [start, stop) and the row: not on the number of channels.
+// the chunk in registers (HdChunk, rowpass.h).  What a chunk computes depends on nothing but [start, stop) and the row:
+// not on the number of channels.
 //
 //   hg_edges_kernel    the edges travel to the device BY VALUE, 256 float64 per launch (at most five launches for 1025
 //                      edges, one for the 50 of the reference): no upload, no host synchronisation, the host array is
@@ -33,47 +32,24 @@
 // Determinism: the only atomics are integer adds (LDS 32-bit, global 64-bit), whose sum does not depend on arrival order;
 // the float64 sums are merged in a fixed order.  The same call gives the same bytes twice, and a workgroup never looks at
 // another channel's data.  Index arithmetic on the array is 64-bit.
-#include "common.h"
+#include "rowpass.h"
 #include <cmath>
 
 namespace {
 
 constexpr int HG_THREADS = 256;
 constexpr int HG_VEC = 16;                              // 16-byte loads per thread and chunk
-constexpr int HG_CHUNK = HG_THREADS * HG_VEC * 4;       // elements per chunk
+typedef HdChunk<HG_THREADS, HG_VEC> HgChunk;
+constexpr int HG_CHUNK = HgChunk::CHUNK;                // elements per chunk
 constexpr int HG_MAX_BINS = 1024;
 constexpr int HG_ROUNDS = 2;                            // ballot rounds before the lanes add one by one
 constexpr int HG_EDGE_BATCH = 256;                      // edges per hg_edges_kernel launch (2 KiB of kernel arguments)
-constexpr long long HG_MAX_CHANNELS = 65535;            // grid.y
 
 typedef unsigned long long u64;
 
 struct EdgeBatch {
     double e[HG_EDGE_BATCH];
 };
-
-// where the samples of a chunk are: [0, head) single samples up to the first 16-byte boundary, then nvec whole vectors,
-// then tail < 4 samples
-struct ChunkShape {
-    const float *p;
-    const float4 *vp;
-    int head, nvec, tail;
-};
-
-__device__ __forceinline__ ChunkShape hg_chunk(const float *row, long long start, long long stop, long long j)
-{
-    ChunkShape s;
-    const long long b0 = start + j * HG_CHUNK;
-    const long long left = stop - b0;
-    const int len = left < HG_CHUNK ? (int)left : HG_CHUNK;
-    s.p = row + b0;
-    s.head = (int)((4u - (unsigned)(((uintptr_t)s.p >> 2) & 3u)) & 3u);
-    if (s.head > len) s.head = len;
-    s.nvec = (len - s.head) >> 2;
-    s.tail = len - s.head - 4 * s.nvec;
-    s.vp = (const float4 *)(s.p + s.head);
-    return s;
-}
 
 __global__ __launch_bounds__(HG_EDGE_BATCH) void hg_edges_kernel(EdgeBatch b, int at, int n, double *__restrict__ dst)
 {
@@ -157,17 +133,12 @@ __global__ __launch_bounds__(HG_THREADS) void hg_count_kernel(const float *__res
     const int S = B + 3;
     const int t = threadIdx.x, lane = t & 63;
     const long long j = blockIdx.x, c = blockIdx.y;
-    const ChunkShape s = hg_chunk(x + c * pitch, start, stop, j);
+    const HgChunk s(x + c * pitch, start, stop, j);
 
     const float nosample = __uint_as_float(0x7fc00000u);
     float4 v[HG_VEC];
-#pragma unroll
-    for (int u = 0; u < HG_VEC; u++) {
-        const int i = u * HG_THREADS + t;
-        v[u] = i < s.nvec ? s.vp[i] : make_float4(nosample, nosample, nosample, nosample);
-    }
-    const float hx = t < s.head ? s.p[t] : nosample;
-    const float tx = t < s.tail ? s.p[s.head + 4 * s.nvec + t] : nosample;
+    float hx, tx;
+    s.load(t, nosample, v, hx, tx);
 
     for (int i = t; i <= B; i += HG_THREADS) e[i] = edges[i];
     for (int i = t; i < 4 * S; i += HG_THREADS) tab[i] = 0;
@@ -220,18 +191,13 @@ __global__ __launch_bounds__(HG_THREADS) void mask_partial_kernel(const float *_
     __shared__ int sh_n[4];
     const int t = threadIdx.x;
     const long long j = blockIdx.x, c = blockIdx.y;
-    const ChunkShape s = hg_chunk(x + c * pitch, start, stop, j);
+    const HgChunk s(x + c * pitch, start, stop, j);
     const double lo = bounds[3 * c], hi = bounds[3 * c + 1], K = bounds[3 * c + 2];
 
     const float nosample = __uint_as_float(0x7fc00000u);        // a NaN is never selected
     float4 v[HG_VEC];
-#pragma unroll
-    for (int u = 0; u < HG_VEC; u++) {
-        const int i = u * HG_THREADS + t;
-        v[u] = i < s.nvec ? s.vp[i] : make_float4(nosample, nosample, nosample, nosample);
-    }
-    const float hx = t < s.head ? s.p[t] : nosample;
-    const float tx = t < s.tail ? s.p[s.head + 4 * s.nvec + t] : nosample;
+    float hx, tx;
+    s.load(t, nosample, v, hx, tx);
 
     MaskLane l;
 #pragma unroll
@@ -263,8 +229,7 @@ __global__ __launch_bounds__(HG_THREADS) void mask_partial_kernel(const float *_
     __syncthreads();
     if (t == 0) {
         MaskPartial q;
-        q.s1 = (sh_s1[0] + sh_s1[1]) + (sh_s1[2] + sh_s1[3]);
-        q.s2 = (sh_s2[0] + sh_s2[1]) + (sh_s2[2] + sh_s2[3]);
+        hd_moments_block(sh_s1, sh_s2, q.s1, q.s2);
         q.n = (long long)((sh_n[0] + sh_n[1]) + (sh_n[2] + sh_n[3]));
         part[c * n_chunks + j] = q;
     }
@@ -305,14 +270,7 @@ __global__ __launch_bounds__(HG_THREADS) void mask_finish_kernel(const double *_
     if (t != 0) return;
     const double nan = __longlong_as_double(0x7ff8000000000000LL);
     double mean = nan, sd = nan;
-    if (n > 0) {
-        const double K = bounds[3 * c + 2];
-        const double md = s1 / (double)n;
-        double var = s2 / (double)n - md * md;
-        if (!(var > 0.0)) var = 0.0;
-        mean = K + md;
-        sd = sqrt(var);
-    }
+    if (n > 0) hd_moments_finish(s1, s2, (double)n, bounds[3 * c + 2], mean, sd);
     double *o = out + c * 4;
     o[0] = (double)n;
     o[1] = mean;
@@ -324,17 +282,10 @@ __global__ __launch_bounds__(HG_THREADS) void mask_finish_kernel(const double *_
 int hg_check_rows(hipdsp_ctx *ctx, const float *x, int64_t x_pitch, int64_t channels, int64_t start, int64_t stop,
                   long long *n_chunks)
 {
-    HD_REQUIRE(ctx != nullptr, "ctx is NULL");
-    HD_REQUIRE(channels >= 0, "negative number of channels");
-    HD_REQUIRE(start >= 0 && start <= stop, "elements [%lld, %lld) are no range", (long long)start, (long long)stop);
+    HD_TRY(hd_check_rows(ctx, channels, start, stop));
     HD_REQUIRE(x_pitch >= 0, "negative x_pitch");
-    if (channels > HG_MAX_CHANNELS) {
-        hipdsp_set_error("at most %lld channels per call, got %lld", HG_MAX_CHANNELS, (long long)channels);
-        return HIPDSP_ERR_UNSUPPORTED;
-    }
-    HD_REQUIRE(x_pitch >= stop || channels <= 1, "x_pitch smaller than stop");
-    HD_REQUIRE(x != nullptr || stop == start || channels == 0, "NULL data pointer");
-    HD_REQUIRE(((uintptr_t)x & 3) == 0, "x is not aligned to 4 bytes");
+    HD_TRY(hd_check_rows_limits(channels, stop - start, 0));
+    HD_TRY(hd_check_rows_x(x, x_pitch, channels, start, stop));
     *n_chunks = (stop - start) / HG_CHUNK + ((stop - start) % HG_CHUNK != 0);
     HD_REQUIRE(*n_chunks <= 0x7fffffffLL, "too many elements for one call");
     return HIPDSP_OK;

@@ -17,8 +17,8 @@
 //                     holds a NaN: nothing is <= NaN, so such a block is never skipped) go to the bottom level of the
 //                     min/max table, and their reduction over the wave to the chunk level.  The chunk's last run start
 //                     (a position whose predecessor is not equal to it) is recorded.
-//   pk_carry_kernel   one workgroup per channel: exclusive prefix maximum of the last run starts along the chunks (the
-//                     shape of ev_carry_kernel), and the table's top level, one entry per 64 chunks.
+//   pk_carry_kernel   one workgroup per channel: exclusive prefix maximum of the last run starts along the chunks
+//                     (hd_scan_exclusive, rowpass.h), and the table's top level, one entry per 64 chunks.
 //   pk_count_kernel   per fall bit: l from the equal bits (or the carried run start), the rise bit at l, m = (l + r)/2,
 //                     height and threshold at m, then -- only if a prominence border is closed -- the prominence.
 //                     The peaks kept are counted and their bits stored.
@@ -39,8 +39,7 @@
 // call gives the same bytes twice, and a channel's result depends on no other channel.  All comparisons are float32
 // comparisons of the samples, which are the float64 comparisons of the exactly converted samples; differences are taken
 // in float64.  Index arithmetic on the array is 64-bit.
-#include "common.h"
-#include <cmath>
+#include "rowpass.h"
 
 namespace {
 
@@ -48,8 +47,6 @@ constexpr int PK_WORDS = 64;                            // 64-bit words of bits 
 constexpr int PK_CHUNK = PK_WORDS * 64;                 // samples per chunk
 constexpr long long PK_SUPER = 64LL * PK_CHUNK;         // samples per entry of the table's top level
 constexpr int PK_SCAN_THREADS = 256;
-constexpr long long PK_MAX_FRAMES = 1LL << 40;          // stop - start of one call
-constexpr long long PK_MAX_CHANNELS = 65535;            // grid.y
 
 typedef unsigned long long u64;
 
@@ -60,6 +57,25 @@ struct PkWork {                                         // the scratch of one ca
     float *smin, *smax;                                 // [channel][n_super]: per 64 chunks
     long long *runstart;                                // last run start of the chunk -> of everything before it
     long long *slot;                                    // peaks kept in the chunk -> the chunk's first output slot
+
+    // the arrays of `per` (channel, chunk) pairs and `sup` (channel, 64 chunks) pairs over `block`: their bytes
+    size_t carve(void *block, size_t per, size_t sup)
+    {
+        HdCarve c(block);
+        rise = c.take<u64>(per * PK_WORDS);
+        fall = c.take<u64>(per * PK_WORDS);
+        eq = c.take<u64>(per * PK_WORDS);
+        kept = c.take<u64>(per * PK_WORDS);
+        runstart = c.take<long long>(per);
+        slot = c.take<long long>(per);
+        bmin = c.take<float>(per * PK_WORDS);
+        bmax = c.take<float>(per * PK_WORDS);
+        cmin = c.take<float>(per);
+        cmax = c.take<float>(per);
+        smin = c.take<float>(sup);
+        smax = c.take<float>(sup);
+        return c.bytes();
+    }
 };
 
 struct PkBorders {
@@ -69,30 +85,6 @@ struct PkBorders {
 struct PkTab {                                          // the min/max table of one channel
     const float *bmin, *bmax, *cmin, *cmax, *smin, *smax;
 };
-
-__device__ __forceinline__ long long pk_wave_max(long long v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const long long o = __shfl_xor(v, d, 64);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
-__device__ __forceinline__ float pk_wave_fmin(float v)  // NaN operands are ignored
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = fminf(v, __shfl_xor(v, d, 64));
-    return v;
-}
-
-__device__ __forceinline__ float pk_wave_fmax(float v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
-    return v;
-}
 
 // run starts of a lane's word: positions whose predecessor is not equal to them; `before` = the equal bit of the sample
 // before the word
@@ -129,8 +121,8 @@ __global__ __launch_bounds__(64) void pk_bits_kernel(const float *__restrict__ x
                 eq = e;
             }
             if (TABLE) {
-                const float lo = pk_wave_fmin(v[u]);
-                const float hi = __ballot(v[u] != v[u]) ? NAN : pk_wave_fmax(v[u]);
+                const float lo = hd_wave_fmin(v[u]);
+                const float hi = __ballot(v[u] != v[u]) ? NAN : hd_wave_fmax(v[u]);
                 if (lane == i0 + u) {
                     mymin = lo;
                     mymax = hi;
@@ -146,8 +138,8 @@ __global__ __launch_bounds__(64) void pk_bits_kernel(const float *__restrict__ x
     if (TABLE) {
         w.bmin[at] = mymin;
         w.bmax[at] = mymax;
-        const float lo = pk_wave_fmin(mymin);
-        const float hi = __ballot(mymax != mymax) ? NAN : pk_wave_fmax(mymax);
+        const float lo = hd_wave_fmin(mymin);
+        const float hi = __ballot(mymax != mymax) ? NAN : hd_wave_fmax(mymax);
         if (lane == 0) {
             w.cmin[cj] = lo;
             w.cmax[cj] = hi;
@@ -159,7 +151,7 @@ __global__ __launch_bounds__(64) void pk_bits_kernel(const float *__restrict__ x
     const long long p0 = base + (long long)lane * 64;
     const u64 inside = stop - p0 >= 64 ? ~(u64)0 : stop - p0 <= 0 ? 0 : ((u64)1 << (stop - p0)) - 1;
     const u64 starts = pk_run_starts(eq, lane == 0 ? entered : (bool)(up >> 63)) & inside;
-    const long long last = pk_wave_max(starts ? p0 + 63 - __clzll((long long)starts) : -1);
+    const long long last = hd_wave_max(starts ? p0 + 63 - __clzll((long long)starts) : -1);
     if (lane == 0) w.runstart[cj] = last;
 }
 
@@ -168,28 +160,7 @@ __global__ __launch_bounds__(PK_SCAN_THREADS) void pk_carry_kernel(long long n_c
 {
     __shared__ long long sh[PK_SCAN_THREADS];
     const int t = threadIdx.x;
-    long long *rs = w.runstart + (long long)blockIdx.x * n_chunks;
-    const long long per = (n_chunks + PK_SCAN_THREADS - 1) / PK_SCAN_THREADS;
-    const long long a = per * t < n_chunks ? per * t : n_chunks, b = a + per < n_chunks ? a + per : n_chunks;
-    long long m = -1;
-    for (long long i = a; i < b; i++) m = rs[i] > m ? rs[i] : m;
-    sh[t] = m;
-    __syncthreads();
-    if (t == 0) {
-        long long run = -1;
-        for (int k = 0; k < PK_SCAN_THREADS; k++) {
-            const long long v = sh[k];
-            sh[k] = run;
-            run = v > run ? v : run;
-        }
-    }
-    __syncthreads();
-    long long run = sh[t];
-    for (long long i = a; i < b; i++) {
-        const long long v = rs[i];
-        rs[i] = run;
-        run = v > run ? v : run;
-    }
+    hd_scan_exclusive<PK_SCAN_THREADS, false>(w.runstart + (long long)blockIdx.x * n_chunks, n_chunks, sh, t, -1, HdMaxOp());
     if (!table) return;
     const float *cmin = w.cmin + (long long)blockIdx.x * n_chunks, *cmax = w.cmax + (long long)blockIdx.x * n_chunks;
     for (long long k = t; k < n_super; k += PK_SCAN_THREADS) {
@@ -419,29 +390,8 @@ __global__ __launch_bounds__(PK_SCAN_THREADS) void pk_slots_kernel(long long n_c
     __shared__ long long sh[PK_SCAN_THREADS];
     __shared__ long long sh_total;
     const int t = threadIdx.x;
-    long long *slot = w.slot + (long long)blockIdx.x * n_chunks;
-    const long long per = (n_chunks + PK_SCAN_THREADS - 1) / PK_SCAN_THREADS;
-    const long long a = per * t < n_chunks ? per * t : n_chunks, b = a + per < n_chunks ? a + per : n_chunks;
-    long long sum = 0;
-    for (long long i = a; i < b; i++) sum += slot[i];
-    sh[t] = sum;
-    __syncthreads();
-    if (t == 0) {
-        long long acc = 0;
-        for (int k = 0; k < PK_SCAN_THREADS; k++) {
-            const long long v = sh[k];
-            sh[k] = acc;
-            acc += v;
-        }
-        sh_total = acc;
-    }
-    __syncthreads();
-    long long run = sh[t];
-    for (long long i = a; i < b; i++) {
-        const long long v = slot[i];
-        slot[i] = run;
-        run += v;
-    }
+    hd_scan_exclusive<PK_SCAN_THREADS, false>(w.slot + (long long)blockIdx.x * n_chunks, n_chunks, sh, t, 0, HdSumOp(),
+                                              &sh_total);
     if (t == 0) counts[blockIdx.x] = sh_total;
 }
 
@@ -459,13 +409,7 @@ __global__ __launch_bounds__(64) void pk_emit_kernel(const float *__restrict__ x
     const PkTab tab = pk_table(w, n_chunks, n_super, c);
     const u64 kept = w.kept[cj * PK_WORDS + lane];
     const int mine = __popcll(kept);
-    int incl = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += o;
-    }
-    long long at = w.slot[cj] + (incl - mine);
+    long long at = w.slot[cj] + hd_wave_exclusive(mine, lane);
     for (u64 f = kept; f && at < capacity; f &= f - 1, at++) {
         const int b = __ffsll((long long)f) - 1;
         long long m;
@@ -492,23 +436,14 @@ extern "C" int hipdsp_find_peaks(hipdsp_ctx *ctx, const float *x, int64_t x_pitc
                                  double tmax, double pmin, double pmax, int64_t wlen, int64_t capacity, int64_t *peaks,
                                  int64_t peaks_pitch, double *props, int64_t props_pitch, int64_t *counts)
 {
-    HD_REQUIRE(ctx != nullptr, "ctx is NULL");
-    HD_REQUIRE(channels >= 0, "negative number of channels");
-    HD_REQUIRE(start >= 0 && start <= stop, "elements [%lld, %lld) are no range", (long long)start, (long long)stop);
+    HD_TRY(hd_check_rows(ctx, channels, start, stop));
     HD_REQUIRE(wlen >= 0, "negative wlen");
     HD_REQUIRE(capacity >= 0, "negative capacity");
     if (peaks_pitch == 0) peaks_pitch = capacity;
     if (props_pitch == 0) props_pitch = 4 * capacity;
     HD_REQUIRE(peaks_pitch >= capacity, "peaks_pitch smaller than capacity");
     HD_REQUIRE(props_pitch >= 4 * capacity, "props_pitch smaller than 4*capacity");
-    if (channels > PK_MAX_CHANNELS) {
-        hipdsp_set_error("at most %lld channels per call, got %lld", PK_MAX_CHANNELS, (long long)channels);
-        return HIPDSP_ERR_UNSUPPORTED;
-    }
-    if (stop - start > PK_MAX_FRAMES) {
-        hipdsp_set_error("at most 2^40 elements per row and call, got %lld", (long long)(stop - start));
-        return HIPDSP_ERR_UNSUPPORTED;
-    }
+    HD_TRY(hd_check_rows_limits(channels, stop - start, HD_MAX_FRAMES));
     if (channels == 0) return HIPDSP_OK;
     HD_REQUIRE(counts != nullptr, "counts is NULL");
     HD_REQUIRE(peaks != nullptr || capacity == 0, "peaks is NULL with a capacity of %lld", (long long)capacity);
@@ -520,29 +455,15 @@ extern "C" int hipdsp_find_peaks(hipdsp_ctx *ctx, const float *x, int64_t x_pitc
         HD_CHECK_HIP(hipMemsetAsync(counts, 0, sizeof(int64_t) * (size_t)channels, ctx->stream));
         return HIPDSP_OK;
     }
-    HD_REQUIRE(x != nullptr, "NULL data pointer");
-    HD_REQUIRE(((uintptr_t)x & 3) == 0, "x is not aligned to 4 bytes");
-    HD_REQUIRE(x_pitch >= stop || channels == 1, "x_pitch smaller than stop");
+    HD_TRY(hd_check_rows_x(x, x_pitch, channels, start, stop));
     if (capacity == 0) props = nullptr;
     const long long n_chunks = (stop - start + PK_CHUNK - 1) / PK_CHUNK;
     const long long n_super = (n_chunks + 63) / 64;
     const size_t per = (size_t)n_chunks * (size_t)channels, sup = (size_t)n_super * (size_t)channels;
-    void *work = nullptr;
-    int rc = hipdsp_scratch(ctx, per * (4 * PK_WORDS * 8 + 2 * PK_WORDS * 4 + 24) + sup * 8, &work);
-    if (rc != HIPDSP_OK) return rc;
     PkWork w;
-    w.rise = (u64 *)work;
-    w.fall = w.rise + per * PK_WORDS;
-    w.eq = w.fall + per * PK_WORDS;
-    w.kept = w.eq + per * PK_WORDS;
-    w.runstart = (long long *)(w.kept + per * PK_WORDS);
-    w.slot = w.runstart + per;
-    w.bmin = (float *)(w.slot + per);
-    w.bmax = w.bmin + per * PK_WORDS;
-    w.cmin = w.bmax + per * PK_WORDS;
-    w.cmax = w.cmin + per;
-    w.smin = w.cmax + per;
-    w.smax = w.smin + sup;
+    void *work = nullptr;
+    HD_TRY(hipdsp_scratch(ctx, w.carve(nullptr, per, sup), &work));
+    w.carve(work, per, sup);
     PkBorders bd = {{hmin, hmax, tmin, tmax, pmin, pmax}};
     // the min/max table serves the prominence search only: per-channel borders on the device may ask for it
     const bool table = props != nullptr || dev_borders != nullptr || !(pmin == -INFINITY && pmax == INFINITY);

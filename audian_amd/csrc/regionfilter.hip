@@ -1,7 +1,8 @@
 // hipdsp_region_filtfilt and hipdsp_region_crossings: the two device steps of the reference's event refinement
 // (filter_envelopes, songdetector.py:178-192, and analyse_songs, :195-244; the contracts are in include/hip_dsp.h).
-// Both take a host table of (channel, start, stop) regions like hipdsp_region_spectra, size a flat work list exactly
-// from it and compute a region from nothing but its own samples and parameters.
+// Both take a host table of (channel, start, stop) regions like hipdsp_region_spectra (hd_check_table, hd_upload_table
+// and hd_owner of rowpass.h), size a flat work list exactly from it and compute a region from nothing but its own
+// samples and parameters.
 //
 // hipdsp_region_filtfilt -- scipy.signal.sosfiltfilt of every region with the region's OWN one- or two-section filter.
 // A region of L samples is extended oddly by padlen on both sides to E = L + 2 padlen samples; that sequence is cut into
@@ -29,8 +30,7 @@
 // largest sample and its position.  rc_chunk: one 256-thread workgroup per chunk of RC_CHUNK = 4096 samples counted from
 // the region's start reduces (count, first, last, max, argmax) in a fixed order; rc_finish: one thread per region merges
 // the chunks in ascending order.  Integers and comparisons only: exact.
-#include "common.h"
-#include <cmath>
+#include "rowpass.h"
 #include <vector>
 #include <algorithm>
 
@@ -89,17 +89,6 @@ __device__ __forceinline__ double rf_ext(const float *__restrict__ v, long long 
     return 2.0 * (double)v[len - 1] - (double)v[2 * len + pad - 2 - i];
 }
 
-__device__ __forceinline__ int rf_find(const RfRegion *__restrict__ tab, int n_regions, long long g)
-{
-    int lo = 0, hi = n_regions - 1;                     // the last region whose first tile is <= g
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (tab[mid].tbase <= g) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
 // BWD: position j of the reversed forward pass, j = E - 1 - i.  WRITE: from the true states, storing the result.
 template <int S, bool BWD, bool WRITE>
 __global__ __launch_bounds__(64) void rf_pass(const float *__restrict__ x, long long x_pitch, float *__restrict__ y,
@@ -110,7 +99,7 @@ __global__ __launch_bounds__(64) void rf_pass(const float *__restrict__ x, long 
     __shared__ double tile[64 * RF_ROW];
     const int lane = threadIdx.x;
     const long long g = blockIdx.x;
-    const int r = rf_find(tab, n_regions, g);
+    const int r = hd_owner(tab, &RfRegion::tbase, n_regions, g);
     const RfRegion &reg = tab[r];
     const long long len = reg.len, pad = reg.pad, E = len + 2 * pad;
     const long long t0 = (g - reg.tbase) * RF_TILE;     // first position of the tile
@@ -293,35 +282,6 @@ int rf_launch(hipdsp_ctx *ctx, const float *x, long long x_pitch, float *y, long
     return hd_launch_status("rf_pass (backward)");
 }
 
-// the checks both entry points share; 0 = fine
-int table_checks(const char *who, hipdsp_ctx *ctx, const float *x, int64_t &x_pitch, int64_t channels, int64_t frames,
-                 const int64_t *host_regions, int64_t n_regions)
-{
-    HD_REQUIRE(ctx != nullptr, "ctx is NULL");
-    HD_REQUIRE(channels >= 0 && frames >= 0 && n_regions >= 0, "negative size");
-    if (x_pitch == 0) x_pitch = frames;
-    HD_REQUIRE(x_pitch >= frames, "x_pitch smaller than frames");
-    if (n_regions == 0) return HIPDSP_OK;
-    HD_REQUIRE(host_regions != nullptr, "NULL region table");
-    HD_REQUIRE(x != nullptr, "NULL data pointer");
-    HD_REQUIRE(((uintptr_t)x & 3) == 0, "misaligned pointer");
-    HD_REQUIRE(n_regions < (1LL << 31) / 64, "too many regions for one call (%lld)", (long long)n_regions);
-    for (int64_t r = 0; r < n_regions; r++) {
-        const int64_t c = host_regions[3 * r], a = host_regions[3 * r + 1], b = host_regions[3 * r + 2];
-        HD_REQUIRE(c >= 0 && c < channels, "region %lld: channel %lld not in [0, %lld)", (long long)r, (long long)c,
-                   (long long)channels);
-        HD_REQUIRE(a >= 0 && a <= b && b <= frames, "region %lld: elements [%lld, %lld) not inside [0, %lld]", (long long)r,
-                   (long long)a, (long long)b, (long long)frames);
-    }
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (ctx->stream) (void)hipStreamIsCapturing(ctx->stream, &st);
-    if (st != hipStreamCaptureStatusNone) {
-        hipdsp_set_error("%s reads its region table from host memory: not during stream capture", who);
-        return HIPDSP_ERR_INVALID;
-    }
-    return HIPDSP_OK;
-}
-
 // A^(64 * 2^b), b = 0 ... 6, of the cascade's state transition (input zero), n = 2 S states: squared in long double, every
 // power rounded once
 void transition_powers(const double c[2][5], int S, double P[7][16])
@@ -368,10 +328,11 @@ extern "C" int hipdsp_region_filtfilt(hipdsp_ctx *ctx, const float *x, int64_t x
         return HIPDSP_ERR_UNSUPPORTED;
     }
     if (y_pitch == 0) y_pitch = frames;
-    int rc = table_checks("hipdsp_region_filtfilt", ctx, x, x_pitch, channels, frames, host_regions, n_regions);
-    if (rc != HIPDSP_OK) return rc;
+    HD_TRY(hd_check_table("hipdsp_region_filtfilt", ctx, x, x_pitch, channels, frames, host_regions, n_regions,
+                          (1LL << 31) / 64));
     HD_REQUIRE(y_pitch >= frames, "y_pitch smaller than frames");
     if (n_regions == 0) return HIPDSP_OK;
+    HD_REQUIRE(x != nullptr, "NULL data pointer");
     HD_REQUIRE(y != nullptr && host_sos != nullptr, "NULL output or filter table");
     HD_REQUIRE(((uintptr_t)y & 3) == 0, "misaligned pointer");
     if (!((const float *)y == x && y_pitch == x_pitch))
@@ -448,16 +409,13 @@ extern "C" int hipdsp_region_filtfilt(hipdsp_ctx *ctx, const float *x, int64_t x
     const size_t fwd_bytes = sizeof(double) * (size_t)samples, st_bytes = sizeof(double) * 2 * S * (size_t)chunks;
     const size_t ts_bytes = sizeof(double) * 2 * S * (size_t)tiles;
     void *work = nullptr;
-    rc = hipdsp_scratch(ctx, tab_bytes + fwd_bytes + st_bytes + ts_bytes + 8 * (size_t)n_regions, &work);
-    if (rc != HIPDSP_OK) return rc;
+    HD_TRY(hipdsp_scratch(ctx, tab_bytes + fwd_bytes + st_bytes + ts_bytes + 8 * (size_t)n_regions, &work));
     const RfRegion *dtab = (const RfRegion *)work;
     double *fwd = (double *)((char *)work + tab_bytes);
     double *states = (double *)((char *)work + tab_bytes + fwd_bytes);
     double *tstate = (double *)((char *)work + tab_bytes + fwd_bytes + st_bytes);
     int *bad = (int *)((char *)work + tab_bytes + fwd_bytes + st_bytes + ts_bytes);
-    // the table is a local: the copy has to be complete before it goes away
-    HD_CHECK_HIP(hipMemcpyAsync(work, tab.data(), tab_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HD_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    HD_TRY(hd_upload_table(ctx, work, tab.data(), tab_bytes));
     if (S == 1)
         return rf_launch<1>(ctx, x, x_pitch, y, y_pitch, dtab, (int)n_regions, tiles, fwd, states, tstate, bad, clamp != 0);
     return rf_launch<2>(ctx, x, x_pitch, y, y_pitch, dtab, (int)n_regions, tiles, fwd, states, tstate, bad, clamp != 0);
@@ -509,13 +467,7 @@ __global__ __launch_bounds__(RC_THREADS) void rc_chunk(const float *__restrict__
     __shared__ RcPart sh[RC_THREADS / 64];
     const int t = threadIdx.x;
     const long long g = blockIdx.x;
-    int lo = 0, hi = n_regions - 1;                     // the last region whose first chunk is <= g (empty ones own none)
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (tab[mid].ibase <= g) lo = mid;
-        else hi = mid - 1;
-    }
-    const RcRegion reg = tab[lo];
+    const RcRegion reg = tab[hd_owner(tab, &RcRegion::ibase, n_regions, g)];
     const long long c0 = (g - reg.ibase) * RC_CHUNK;
     const long long left = reg.len - c0;
     const int n = left < RC_CHUNK ? (int)left : RC_CHUNK;
@@ -591,9 +543,10 @@ extern "C" int hipdsp_region_crossings(hipdsp_ctx *ctx, const float *x, int64_t 
                                        const int64_t *host_regions, const double *host_thresholds, int64_t n_regions,
                                        double *out)
 {
-    int rc = table_checks("hipdsp_region_crossings", ctx, x, x_pitch, channels, frames, host_regions, n_regions);
-    if (rc != HIPDSP_OK) return rc;
+    HD_TRY(hd_check_table("hipdsp_region_crossings", ctx, x, x_pitch, channels, frames, host_regions, n_regions,
+                          (1LL << 31) / 64));
     if (n_regions == 0) return HIPDSP_OK;
+    HD_REQUIRE(x != nullptr, "NULL data pointer");
     HD_REQUIRE(host_thresholds != nullptr && out != nullptr, "NULL thresholds or output");
     HD_REQUIRE(((uintptr_t)out & 7) == 0, "misaligned pointer");
     std::vector<RcRegion> tab((size_t)n_regions + 1);
@@ -608,13 +561,11 @@ extern "C" int hipdsp_region_crossings(hipdsp_ctx *ctx, const float *x, int64_t 
     HD_CHECK_HIP(hipSetDevice(ctx->device));
     const size_t tab_bytes = sizeof(RcRegion) * tab.size();
     void *work = nullptr;
-    rc = hipdsp_scratch(ctx, tab_bytes + sizeof(RcPart) * (size_t)items, &work);
+    int rc = hipdsp_scratch(ctx, tab_bytes + sizeof(RcPart) * (size_t)items, &work);
     if (rc != HIPDSP_OK) return rc;
     const RcRegion *dtab = (const RcRegion *)work;
     RcPart *part = (RcPart *)((char *)work + tab_bytes);
-    // the table is a local: the copy has to be complete before it goes away
-    HD_CHECK_HIP(hipMemcpyAsync(work, tab.data(), tab_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HD_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    HD_TRY(hd_upload_table(ctx, work, tab.data(), tab_bytes));
     if (items > 0) {
         hipLaunchKernelGGL(rc_chunk, dim3((unsigned)items), dim3(RC_THREADS), 0, ctx->stream, x, (long long)x_pitch, dtab,
                            (int)n_regions, part);

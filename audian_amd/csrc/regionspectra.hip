@@ -8,7 +8,7 @@
 //   region_spectra_kernel   one 256-thread workgroup per (region, frame group).  The groups of a region are anchored at
 //                           the region's FIRST frame and hold SP_GROUP = 16 consecutive frames (the last one fewer), so
 //                           what a group computes depends on nothing but the region and (nfft, hop, step).  The workgroup
-//                           finds its region by a binary search over the table's item offsets, builds exp(-2 pi i m /
+//                           finds its region by hd_owner (rowpass.h) over the table's item offsets, builds exp(-2 pi i m /
 //                           nfft), m < nfft/2, once in LDS (float64 sincospi, rounded to float32; the Hann window is
 //                           0.5 -+ 0.5 cos from the same table) and then takes frame after frame: the samples x[start +
 //                           (k*hop + i)*step] go to LDS while their float64 sum is reduced in a fixed order; the mean is
@@ -26,8 +26,7 @@
 //
 // LDS: 12 * nfft bytes (two buffers of nfft/2 float2 and the table), 96 KB at nfft 8192.  No atomics at all: the same
 // call gives the same bytes twice, whatever else rides in it.  Index arithmetic on the array is 64-bit.
-#include "common.h"
-#include <cmath>
+#include "rowpass.h"
 #include <vector>
 
 namespace {
@@ -52,13 +51,7 @@ __global__ __launch_bounds__(SP_THREADS) void region_spectra_kernel(const float 
     const int M = nfft >> 1, F = M + 1, half = M >> 1;
     float2 *A = sp_lds, *B = sp_lds + M, *tw = sp_lds + 2 * M;
 
-    int lo = 0, hi = n_regions - 1;                     // the last region whose first item is <= g (empty ones own none)
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (tab[mid].ibase <= g) lo = mid;
-        else hi = mid - 1;
-    }
-    const SpRegion reg = tab[lo];
+    const SpRegion reg = tab[hd_owner(tab, &SpRegion::ibase, n_regions, g)];
     const long long k0 = (g - reg.ibase) * SP_GROUP;
     const long long left = reg.n_frames - k0;
     const int nk = left < SP_GROUP ? (int)left : SP_GROUP;
@@ -221,44 +214,31 @@ extern "C" int hipdsp_region_spectra(hipdsp_ctx *ctx, const float *x, int64_t x_
                                      double fs, float *out, int64_t out_pitch, int64_t *info)
 {
     HD_REQUIRE(ctx != nullptr, "ctx is NULL");
-    HD_REQUIRE(channels >= 0 && frames >= 0 && n_regions >= 0, "negative size");
     HD_REQUIRE(nfft >= 8 && nfft <= SP_MAX_NFFT && (nfft & (nfft - 1)) == 0, "nfft %d is not a power of two in [8, %d]", nfft,
                SP_MAX_NFFT);
     HD_REQUIRE(hop >= 1 && hop <= nfft, "hop %d not in [1, nfft = %d]", hop, nfft);
     HD_REQUIRE(step >= 1, "step %lld must be at least 1", (long long)step);
     HD_REQUIRE(fs > 0.0 && fs <= 1.7976931348623157e308, "fs must be positive and finite");
+    HD_TRY(hd_check_table("hipdsp_region_spectra", ctx, x, x_pitch, channels, frames, host_regions, n_regions,
+                          (1LL << 31) / 32));
     const int F = nfft / 2 + 1;
-    if (x_pitch == 0) x_pitch = frames;
     if (out_pitch == 0) out_pitch = F;
-    HD_REQUIRE(x_pitch >= frames, "x_pitch smaller than frames");
     HD_REQUIRE(out_pitch >= F, "out_pitch smaller than nfft/2 + 1");
     if (n_regions == 0) return HIPDSP_OK;
-    HD_REQUIRE(host_regions != nullptr, "NULL region table");
     HD_REQUIRE(out != nullptr && info != nullptr, "NULL output");
-    HD_REQUIRE(((uintptr_t)x & 3) == 0 && ((uintptr_t)out & 3) == 0 && ((uintptr_t)info & 7) == 0, "misaligned pointer");
-    HD_REQUIRE(n_regions < (1LL << 31) / 32, "too many regions for one call (%lld)", (long long)n_regions);
+    HD_REQUIRE(((uintptr_t)out & 3) == 0 && ((uintptr_t)info & 7) == 0, "misaligned pointer");
     std::vector<SpRegion> tab((size_t)n_regions + 1);
     long long items = 0;
     for (int64_t r = 0; r < n_regions; r++) {
-        const int64_t c = host_regions[3 * r], a = host_regions[3 * r + 1], b = host_regions[3 * r + 2];
-        HD_REQUIRE(c >= 0 && c < channels, "region %lld: channel %lld not in [0, %lld)", (long long)r, (long long)c,
-                   (long long)channels);
-        HD_REQUIRE(a >= 0 && a <= b && b <= frames, "region %lld: elements [%lld, %lld) not inside [0, %lld]", (long long)r,
-                   (long long)a, (long long)b, (long long)frames);
+        const int64_t a = host_regions[3 * r + 1], b = host_regions[3 * r + 2];
         const long long len = (b - a + step - 1) / step;                 // len(x[a:b:step])
         const long long nf = len >= nfft ? (len - nfft) / hop + 1 : 0;
-        tab[r] = SpRegion{c, a, nf, items};
+        tab[r] = SpRegion{host_regions[3 * r], a, nf, items};
         items += (nf + SP_GROUP - 1) / SP_GROUP;
     }
     tab[n_regions] = SpRegion{0, 0, 0, items};
     HD_REQUIRE(items <= 0x7fffffffLL, "too many frames for one call");
     HD_REQUIRE(x != nullptr || items == 0, "NULL data pointer");
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (ctx->stream) (void)hipStreamIsCapturing(ctx->stream, &st);
-    if (st != hipStreamCaptureStatusNone) {
-        hipdsp_set_error("hipdsp_region_spectra reads its region table from host memory: not during stream capture");
-        return HIPDSP_ERR_INVALID;
-    }
     HD_CHECK_HIP(hipSetDevice(ctx->device));
     const size_t tab_bytes = sizeof(SpRegion) * tab.size();
     void *work = nullptr;
@@ -266,9 +246,7 @@ extern "C" int hipdsp_region_spectra(hipdsp_ctx *ctx, const float *x, int64_t x_
     if (rc != HIPDSP_OK) return rc;
     const SpRegion *dtab = (const SpRegion *)work;
     double *part = (double *)((char *)work + tab_bytes);
-    // the table is a local: the copy has to be complete before it goes away
-    HD_CHECK_HIP(hipMemcpyAsync(work, tab.data(), tab_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HD_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    HD_TRY(hd_upload_table(ctx, work, tab.data(), tab_bytes));
     double sw2 = 0.0;
     for (int i = 0; i < nfft; i++) {
         const double w = 0.5 - 0.5 * cos(2.0 * M_PI * (double)i / (double)nfft);

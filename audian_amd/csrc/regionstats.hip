@@ -8,11 +8,12 @@
 //                           OWN start and holds RS_CHUNK = 16384 elements per chunk (the last one fewer), so what a
 //                           chunk computes depends on nothing but the region: not on the other regions of the call,
 //                           not on the number of channels.  A thread holds its 64 samples of the chunk in registers
-//                           (sixteen 16-byte loads, all issued before the first use; the up to three samples before
-//                           the first 16-byte boundary and after the last whole vector are loaded one by one), adds
-//                           d = x - K and d*d in float64 (K = the region's first sample, the pivot of the header's
-//                           accuracy contract) and tracks min, max and the largest |x| bit pattern.  The workgroup
-//                           reduces these in a fixed order (wave shuffles, then the four waves through LDS).  Only then
+//                           (HdChunk, rowpass.h: sixteen 16-byte loads, all issued before the first use; the up to
+//                           three samples before the first 16-byte boundary and after the last whole vector are loaded
+//                           one by one), adds d = x - K and d*d in float64 (K = the region's first sample, the pivot of
+//                           the header's accuracy contract) and tracks min, max and the largest |x| bit pattern.  The
+//                           workgroup reduces these in a fixed order (wave shuffles, then the four waves through
+//                           LDS).  Only then
 //                           are positions resolved: a thread whose own minimum equals the workgroup's looks through
 //                           its registers for the first such sample -- no select per sample in the streaming part --
 //                           and the same for the maximum.  Only a chunk whose largest |x| pattern is not finite looks
@@ -25,15 +26,15 @@
 // atomics are integer min / or, which commute), so the same call gives the same bits twice.
 // Per sample: one f32->f64 conversion and four float64 operations, two float32 min/max and two integer operations
 // against 4 bytes read; the float64 VALU rate is not what limits it.  Index arithmetic on the array is 64-bit.
-#include "common.h"
-#include <cmath>
+#include "rowpass.h"
 
 namespace {
 
 constexpr int MAX_REGIONS = 16;
 constexpr int RS_THREADS = 256;
 constexpr int RS_VEC = 16;                              // 16-byte loads per thread and chunk
-constexpr int RS_CHUNK = RS_THREADS * RS_VEC * 4;       // elements per chunk
+typedef HdChunk<RS_THREADS, RS_VEC> RsChunk;
+constexpr int RS_CHUNK = RsChunk::CHUNK;                // elements per chunk
 constexpr int RS_NONE = 0x7fffffff;                     // "no such sample in this chunk"
 constexpr unsigned RS_INF_BITS = 0x7f800000u;
 constexpr unsigned RS_NAN = 1, RS_PINF = 2, RS_NINF = 4;
@@ -85,26 +86,13 @@ __global__ __launch_bounds__(RS_THREADS) void region_partial_kernel(const float 
     const float *row = x + c * pitch;
     const float Kf = row[a.start[r]];
     const double K = (double)Kf;
-    const long long b0 = a.start[r] + j * RS_CHUNK;
-    const long long left = a.stop[r] - b0;
-    const int len = left < RS_CHUNK ? (int)left : RS_CHUNK;
-    const float *p = row + b0;
-    // [0, head): single samples up to the first 16-byte boundary; then nvec whole vectors; then tail < 4 samples
-    int head = (int)((4u - (unsigned)(((uintptr_t)p >> 2) & 3u)) & 3u);
-    if (head > len) head = len;
-    const int nvec = (len - head) >> 2;
-    const int tail = len - head - 4 * nvec;
-    const float4 *vp = (const float4 *)(p + head);
+    const RsChunk s(row, a.start[r], a.stop[r], j);
+    const int head = s.head, nvec = s.nvec, tail = s.tail;
 
     // a slot without a sample holds the pivot: d = 0 there, and K is a sample of the region, so min and max stay right
     float4 v[RS_VEC];
-#pragma unroll
-    for (int u = 0; u < RS_VEC; u++) {
-        const int i = u * RS_THREADS + t;
-        v[u] = i < nvec ? vp[i] : make_float4(Kf, Kf, Kf, Kf);
-    }
-    const float hx = t < head ? p[t] : Kf;
-    const float tx = t < tail ? p[head + 4 * nvec + t] : Kf;
+    float hx, tx;
+    s.load(t, Kf, v, hx, tx);
 
     Lane l;
 #pragma unroll
@@ -217,8 +205,7 @@ __global__ __launch_bounds__(RS_THREADS) void region_partial_kernel(const float 
     __syncthreads();
     if (t == 0) {
         RegionPartial q;
-        q.s1 = (sh_s1[0] + sh_s1[1]) + (sh_s1[2] + sh_s1[3]);
-        q.s2 = (sh_s2[0] + sh_s2[1]) + (sh_s2[2] + sh_s2[3]);
+        hd_moments_block(sh_s1, sh_s2, q.s1, q.s2);
         q.mn = wmn;
         q.mx = wmx;
         q.imin = sh_idx[0];
@@ -310,12 +297,7 @@ __global__ __launch_bounds__(RS_THREADS) void region_finish_kernel(const float *
                 if (!(m.flags & RS_NINF)) mean = (double)INFINITY;
                 else if (!(m.flags & RS_PINF)) mean = -(double)INFINITY;
             } else {
-                const double K = (double)x[c * pitch + a.start[r]];
-                const double md = m.s1 / (double)n;
-                double var = m.s2 / (double)n - md * md;
-                if (!(var > 0.0)) var = 0.0;
-                mean = K + md;
-                sd = sqrt(var);
+                hd_moments_finish(m.s1, m.s2, (double)n, (double)x[c * pitch + a.start[r]], mean, sd);
             }
         }
     }
@@ -343,7 +325,7 @@ extern "C" int hipdsp_region_stats(hipdsp_ctx *ctx, const float *x, int64_t x_pi
         return HIPDSP_ERR_UNSUPPORTED;
     }
     HD_REQUIRE(host_start != nullptr && host_stop != nullptr, "NULL region list");
-    HD_REQUIRE(channels <= 65535, "too many channels for one call (%lld > 65535)", (long long)channels);
+    HD_REQUIRE(channels <= HD_MAX_CHANNELS, "too many channels for one call (%lld > 65535)", (long long)channels);
     if (x_pitch == 0) x_pitch = frames;
     HD_REQUIRE(x_pitch >= frames, "x_pitch smaller than frames");
     RegionArgs a;
