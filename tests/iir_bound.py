@@ -1,5 +1,5 @@
-"""A local accuracy bound for the IIR sweeps (hipdsp_sosfilt, the envelope sweeps, the fused forward sweep), the
-test signals it is applied to and the reference it is measured against.
+"""A local accuracy bound for the IIR sweeps (hipdsp_sosfilt, the envelope sweeps, the fused forward sweep, the
+multi-plan envelope), the test signals it is applied to and the reference it is measured against.
 
 The suite's parity metric (conftest.rel_err) divides a channel's largest error by the channel's loudest sample and
 allows 1e-4: an error that sits where the trace is quiet -- behind a loud passage, behind a segment border where a
@@ -28,11 +28,14 @@ held to that:
   envelope with a high-pass) and between_term (the forward pass handed to the backward pass through the float32 tile:
   envelope plans of three and four sections, the frame-split backward sweep).  Each is the rounding's size times the
   absolute response of the linear pass behind it.
+* hipdsp_envelope_multi runs a cascade plan by plan and writes float32 between the plans: 2P - 1 roundings for P plans,
+  held to handover_term, derived the same way (and to extension_term on both sides where the cascade has a high-pass:
+  odd_ext_kernel forms both extensions in float32).
 * The clamp at zero is judged apart from the arithmetic (envelope_case), and a case's reference must stay in the
   range where the bound can be met at all (assert_in_range).
 
 tests/test_iir_bound.py calibrates all of this on the CPU (the restatement against the C oracle, the cap, the
-correct model inside the bound, two wrong versions outside it); tests/test_gpu_iir_accuracy.py applies it.
+correct model inside the bound, wrong versions outside it); tests/test_gpu_iir_accuracy.py applies it.
 Nothing here imports scipy: designs come from audian_amd.design.butter_sos.
 """
 
@@ -230,6 +233,25 @@ def extension_term(sos, x, gain=GAIN, rectify=True, left=False):
 # keep it in float64 registers).  It sits in the tile loop -- the registers are what the three- and four-section plans
 # lack -- so those two paths are held to the term below instead.
 
+def _responses(sos, N):
+    """(|h|, |s|), (N,) float64 each: the absolute impulse response of a run of sections from zero state, and (where the
+    run starts the cascade) its absolute answer to the state zi alone."""
+    def make():
+        pulse = np.zeros((N, 1))
+        pulse[0] = 1.0
+        zi = sosfilt_zi(sos, np.float64)
+        return (np.abs(sosfilt(sos, pulse, np.float64)[:, 0]),
+                np.abs(sosfilt(sos, np.zeros((N, 1)), np.float64, zi=zi[:, :, None]*np.ones((1, 1, 1)))[:, 0]))
+    return _cached((np.asarray(sos, dtype=np.float64).tobytes(), N, 'h'), make)
+
+
+def _conv(h, w):
+    """sum_(m <= n) h(n - m) w(m, lane), (N, lanes), h and w non-negative, by FFT (negative round-off clipped)."""
+    N = len(w)
+    n = 1 << int(np.ceil(np.log2(2*N)))
+    return np.maximum(np.fft.irfft(np.fft.rfft(h, n)[:, None]*np.fft.rfft(w, n, axis=0), n, axis=0)[:N], 0.0)
+
+
 def between_term(sos, x, gain=GAIN, rectify=True):
     """(T, lanes) float64, per sample: what rounding the forward pass's output y_f to float32 can add to the envelope
     of x.  Sample m of it is off by at most 2^-24 |fl(y_f(m))|; the backward pass is linear with impulse response h and
@@ -245,17 +267,8 @@ def between_term(sos, x, gain=GAIN, rectify=True):
     zi = sosfilt_zi(sos, np.float64)
     yf = sosfilt(sos, ext, np.float64, zi=zi[:, :, None]*ext[0][None, None, :])
     w = (ULP*np.abs(yf.astype(np.float32)).astype(np.float64))[::-1]            # in the backward pass's order
-    N = len(w)
-
-    def make():
-        pulse = np.zeros((N, 1))
-        pulse[0] = 1.0
-        return (np.abs(sosfilt(sos, pulse, np.float64)[:, 0]),
-                np.abs(sosfilt(sos, np.zeros((N, 1)), np.float64, zi=zi[:, :, None]*np.ones((1, 1, 1)))[:, 0]))
-    h, s = _cached((np.asarray(sos, dtype=np.float64).tobytes(), N, 'h'), make)
-    n = 1 << int(np.ceil(np.log2(2*N)))
-    conv = np.fft.irfft(np.fft.rfft(h, n)[:, None]*np.fft.rfft(w, n, axis=0), n, axis=0)[:N]
-    p = np.maximum(conv, 0.0) + s[:, None]*w[0][None, :]
+    h, s = _responses(sos, len(w))
+    p = _conv(h, w) + s[:, None]*w[0][None, :]
     return p[::-1][edge:edge + T]
 
 
@@ -323,6 +336,18 @@ def assert_within(got, ref, q, what, first=0, margin=MARGIN, term=None):
             what, lane, w + first//WINDOW, (w + first//WINDOW)*WINDOW, rho[w, lane], bound[lane],
             (bound[lane] - 1)/margin if margin else 0.0)
     return float(np.max(rho))
+
+
+def allowance_share(got, ref, q, term=None, first=0, margin=MARGIN):
+    """Per lane, the largest e_w / ((1 + margin q) 2^-24 r_w + the term's largest value in the window): the share of the
+    whole allowance that a result uses (above 1 where assert_within fails; inf for a non-zero result where nothing is
+    allowed).  A figure to report next to assert_within, never in its place."""
+    e, r = window_stats(got, ref, first)
+    allowed = (1.0 + margin*np.broadcast_to(np.asarray(q, dtype=np.float64), r.shape))*ULP*r
+    if term is not None:
+        allowed = allowed + np.where(r == 0, 0, window_stats(term, term, first)[1])
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return np.max(np.where(allowed > 0, e/allowed, np.where(e > 0, np.inf, 0.0)), axis=0).astype(np.float64)
 
 
 # ---- the cases: filter x families, shared by the CPU calibration and the GPU tests ---------------------------------
@@ -476,3 +501,173 @@ def envelope_case(sos, x, rectify=True, gain=GAIN):
 def clamped(y):
     """env[env < 0] = 0."""
     return np.where(y < 0, y.dtype.type(0), y)
+
+
+# ---- hipdsp_envelope_multi: a cascade over several plans, float32 between them ------------------------------------------
+# The call runs scipy's sosfiltfilt step by step: the odd extensions by the pad length of the WHOLE cascade, formed in
+# float32 (odd_ext_kernel, both sides); one float64 sweep per plan, each from the whole table's zi for its sections
+# (times the input gain in the first pass), each writing float32; a flip; the same sweeps from zi * y[-1]; a flip that
+# trims.  With P plans that is 2P - 1 float32 roundings the reference does not have (after every plan of the forward
+# pass, after every plan but the last of the backward pass; the last one is the bound's own 1), held to the derived
+# handover_term below.  multi_model restates the call with exactly these roundings for the CPU calibration.
+
+T_MULTI = 8*TILE + 5          # the smallest size at which one segment, three, the planner's choice and one-tile segments
+#                               are four different cuts of N = T + 2 padlen
+
+# label: (order, Wn, btype, rate, families, splits)                                       sections, largest q at T_MULTI
+MULTI = {
+    'lp10 800 Hz @ 48 kHz': (10, 800.0, 'lowpass', 48000.0, NO_ONSET, ((2, 2, 1), (4, 1))),              # 5, 9e-6
+    'lp12 2000 Hz @ 48 kHz': (12, 2000.0, 'lowpass', 48000.0, NO_ONSET, ((3, 3),)),                      # 6, 1.2e-6
+    'bp5 10-500 Hz @ 48 kHz': (5, (10.0, 500.0), 'bandpass', 48000.0, HP_FAMILIES, ((4, 1),)),           # 5, 1.3e-2
+    'bp8 50-4000 Hz @ 48 kHz': (8, (50.0, 4000.0), 'bandpass', 48000.0, HP_FAMILIES, ((4, 4),)),         # 8, 2.8e-4
+    'lp8 60 Hz @ 48 kHz': (8, 60.0, 'lowpass', 48000.0, FAMILIES, ((2, 2), (1, 1, 1, 1))),               # 4, 1.7e-3
+}
+MULTI_SINGLE = 'lp8 60 Hz @ 48 kHz'            # fits one plan too: also run through hipdsp_envelope, under the same reference
+MULTI_SKIP = ('lp10 800 Hz @ 48 kHz', 'bp5 10-500 Hz @ 48 kHz')     # the cases run with `skip`
+MULTI_EDGE = 'bp8 50-4000 Hz @ 48 kHz'         # eight sections: pad length 51
+MULTI_PLAIN = 'lp12 2000 Hz @ 48 kHz'          # run once with rectify 0
+MULTI_GAIN = ('lp10 800 Hz @ 48 kHz', 0.37)    # run once with another gain
+
+
+def multi_design(case):
+    """(sos, rate, families, splits) of a case of MULTI."""
+    from audian_amd.design import butter_sos
+    order, wn, btype, rate, fams, splits = MULTI[case]
+    return butter_sos(order, wn, btype, rate), rate, fams, splits
+
+
+def plan_slices(sos, split):
+    """The sections of every plan of a cascade cut as `split`."""
+    assert sum(split) == len(sos) and min(split) >= 1, (split, len(sos))
+    lo = np.concatenate([[0], np.cumsum(split)])
+    return [slice(int(a), int(b)) for a, b in zip(lo[:-1], lo[1:])]
+
+
+MULTI_WRONG = ('pad length of the last plan', 'float32 state at tile borders', 'one-tile warm-up per segment',
+               'input gain left out of the later plans\' zi', 'backward zi from the extension\'s first sample')
+
+
+def _sweep(sos, x, zi, wrong):
+    """One plan's sweep over the extended sequence in float64, as the kernel is meant to run it -- or as one of the
+    wrong versions does."""
+    if wrong == 'float32 state at tile borders':
+        return sosfilt(sos, x, np.float64, zi=zi, round_state_every=TILE)
+    if wrong == 'one-tile warm-up per segment':                  # two-tile segments, each from zero state one tile before
+        y = np.empty(x.shape, np.float64)
+        for lo in range(0, len(x), 2*TILE):
+            start = max(lo - TILE, 0)
+            y[lo:lo + 2*TILE] = sosfilt(sos, x[start:lo + 2*TILE], np.float64, zi=zi if lo == 0 else None)[lo - start:]
+        return y
+    return sosfilt(sos, x, np.float64, zi=zi)
+
+
+def multi_model(sos, split, x, gain=GAIN, rectify=True, wrong=None):
+    """hipdsp_envelope_multi restated with its roundings, (T, lanes) float32, unclamped: float32 extensions on both sides
+    by the whole cascade's pad length, float64 sweeps, a float32 rounding after every plan of both passes, zi from the
+    whole table.  `wrong`: one of MULTI_WRONG.  A model for the CPU calibration, never a reference."""
+    assert wrong is None or wrong in MULTI_WRONG, wrong
+    x = np.asarray(x)
+    T = len(x)
+    sos = np.asarray(sos, dtype=np.float64)
+    parts = plan_slices(sos, split)
+    edge = padlen(sos[parts[-1]]) if wrong == 'pad length of the last plan' else padlen(sos)
+    r = (np.abs(x) if rectify else x).astype(np.float32)
+    left, right = _ext32(r, edge)
+    cur = np.concatenate([left, r, right]).astype(np.float64)
+    g = float(gain) if rectify else 1.0
+    zi = sosfilt_zi(sos, np.float64)
+    first = cur[0].copy()
+    for backward in (False, True):
+        ref = cur[0].copy()
+        if backward and wrong == 'backward zi from the extension\'s first sample':
+            ref = first
+        for p, part in enumerate(parts):
+            scale = 1.0 if backward else g
+            if p > 0 and wrong == 'input gain left out of the later plans\' zi':
+                scale = 1.0
+            feed = g*cur if (p == 0 and not backward) else cur
+            cur = _sweep(sos[part], feed, zi[part][:, :, None]*(scale*ref)[None, None, :], wrong)
+            cur = cur.astype(np.float32).astype(np.float64)
+        cur = cur[::-1]
+    return cur[edge:edge + T].astype(np.float32)
+
+
+def handover_term(sos, split, x, gain=GAIN, rectify=True):
+    """(T, lanes) float64, per sample: what the 2P - 1 float32 roundings between the plans of hipdsp_envelope_multi can
+    add to the envelope of x.  Derived, not measured:
+
+    * e is the extended sequence (float32-formed extensions, times the gain), v_k the float64 run of plans 1 ... k over
+      it in the forward pass, u_k the same in the backward pass over the reversed v_P.  Rounding k writes fl(v) for a
+      value v and is off by at most 2^-24 max(|v|, |fl(v)|).
+    * Everything behind a rounding is linear.  A forward-pass rounding behind plan j reaches the point behind plan k
+      through the sections of plans j+1 ... k, whose states start from zi e[0], which no rounding touches: it is bounded
+      by the convolution with their absolute impulse response |h_(j,k]|.  What has gathered behind plan P, F(m), goes
+      through the backward pass as in between_term: |h_all| of the whole cascade, plus |s_all(n)| F(last) for the states
+      zi fl(v_P(last)) of EVERY plan of the backward pass (s_all the whole cascade's answer to zi alone).  A
+      backward-pass rounding behind plan j < P reaches the answer through |h_(j,P]|.
+    * The value a rounding sees is v_k plus what the earlier roundings have made of it, so its weight is
+      2^-24 (|v_k| + that earlier term at this very point): this covers the products of two and more roundings
+      exactly, nothing is dropped and no factor is fitted.
+    * The float64 arithmetic of the sweeps is the case's q, as for every other path; the float32 extensions are
+      extension_term's (added by the caller for cascades with a high-pass).
+    Reversed and trimmed to the T samples."""
+    def make():
+        xx = np.asarray(x)
+        T = len(xx)
+        table = np.asarray(sos, dtype=np.float64)
+        parts = plan_slices(table, split)
+        P = len(parts)
+        edge = padlen(table)
+        r = (np.abs(xx) if rectify else xx).astype(np.float32)
+        g = float(gain) if rectify else 1.0
+        left, right = _ext32(r, edge)
+        cur = g*np.concatenate([left, r, right]).astype(np.float64)
+        N = len(cur)
+        zi = sosfilt_zi(table, np.float64)
+
+        pulse = np.zeros((N, 1))
+        pulse[0] = 1.0
+        signed = {}
+
+        def response(j, k):                                     # h of plans j+1 ... k (0-based: parts[j] ... parts[k-1]), plan by plan
+            if (j, k) not in signed:
+                signed[j, k] = sosfilt(table[parts[k - 1]], pulse if k == j + 1 else response(j, k - 1), np.float64)
+            return signed[j, k]
+
+        def between(j, k):
+            return np.abs(response(j, k)[:, 0])
+
+        def rounding(v, earlier):
+            return ULP*(np.maximum(np.abs(v), np.abs(v.astype(np.float32)).astype(np.float64)) + earlier)
+
+        ref = cur[0].copy()
+        weights = []                                            # W_j, the forward pass's roundings
+        for k, part in enumerate(parts, 1):
+            cur = sosfilt(table[part], cur, np.float64, zi=zi[part][:, :, None]*ref[None, None, :])
+            earlier = sum((_conv(between(j, k), weights[j - 1]) for j in range(1, k)), np.zeros_like(cur))
+            weights.append(rounding(cur, earlier))
+            gathered = earlier + weights[-1]
+        d = gathered[::-1]                                      # in the backward pass's order
+        cur = cur[::-1]
+        ref = cur[0].copy()
+        h_all, s_all = _responses(table, N)
+        weights = []                                            # V_j, the backward pass's roundings
+        for k, part in enumerate(parts, 1):
+            cur = sosfilt(table[part], cur, np.float64, zi=zi[part][:, :, None]*ref[None, None, :])
+            h_k, s_k = (h_all, s_all) if k == P else _responses(table[:part.stop], N)
+            earlier = _conv(h_k, d) + s_k[:, None]*d[0][None, :] + \
+                sum((_conv(between(j, k), weights[j - 1]) for j in range(1, k)), np.zeros_like(cur))
+            if k < P:
+                weights.append(rounding(cur, earlier))
+        return earlier[::-1][edge:edge + T]
+    return _cached(_key(sos, x, 'handover', tuple(split), bool(rectify), float(gain)), make)
+
+
+def multi_term(sos, split, x, gain=GAIN, rectify=True):
+    """The whole per-sample allowance of a hipdsp_envelope_multi run on top of the window bound: handover_term, and for a
+    cascade with a high-pass extension_term on both sides (odd_ext_kernel forms both extensions in float32).  A low-pass
+    cascade takes no extension term: the calibration (test_iir_bound.py) shows the model inside the bound without."""
+    term = handover_term(sos, split, x, gain, rectify)
+    if has_highpass(sos):
+        term = term + extension_term(sos, x, gain, rectify, left=True)
+    return term

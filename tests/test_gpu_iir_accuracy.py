@@ -12,8 +12,12 @@ derived terms on top of the bound, on the paths they reach only: the odd extensi
 (iir_bound.extension_term), and the forward pass handed to the backward pass in the float32 tile by the three- and
 four-section envelope sweeps and by the frame-split backward sweep (iir_bound.between_term).
 
-Out of scope: hipdsp_envelope_multi, which hands over in float32 between its plans by design and keeps that term in
-its own test (test_envelope_cascades_longer_than_one_plan).
+hipdsp_envelope_multi (cascades of more than four sections, run plan by plan) is held to the same bound: its 2P - 1
+float32 hand-overs between the P plans take iir_bound.handover_term, both of its float32 extensions extension_term
+where the cascade has a high-pass; 8 tiles + 5 samples, the smallest size at which the four segmentations of the
+extended trace differ.  Its section also covers what only that call has: pitches with slack and odd base offsets, a
+gain other than pi/2, y == x and y over the tail of x (the header's "x and y may overlap"), non-finite samples in one
+lane, the pad length's edge and the limit of 16 plans.
 
 A failure names the path, the filter, the segmentation, the lane (family) and the window; test_zz_worst_per_path
 prints the worst ratio e_w / (2^-24 r_w) of every path measured (run with -s).
@@ -315,13 +319,278 @@ def test_chain_split_frames(bp, env):
     judge_envelopes('chain_split_frames, envelope', esos, runs, 0, 'chain_split_frames, %s + %s' % (bp, env), between=True)
 
 
+# ---- hipdsp_envelope_multi ---------------------------------------------------------------------------------------
+
+MULTI_SPLITS = [(case, split) for case in ib.MULTI for split in ib.MULTI[case][5]]
+
+
+def splitname(split):
+    return '+'.join(str(n) for n in split)
+
+
+def multi_plans(c, sos, split):
+    from audian_amd import hipdsp
+    return [hipdsp.SosPlan(c, sos[part]) for part in ib.plan_slices(sos, split)]
+
+
+def run_multi(c, plans, dx, T, C, skip=0, rectify=True, gain=ib.GAIN, clamp=False):
+    from audian_amd import hipdsp
+    dy = fresh(c, C, T - skip)
+    hipdsp.envelope_multi(c, plans, dx, T, dy, T - skip, C, T, skip, rectify=rectify, gain=gain, clamp=clamp)
+    return dy.to_host().T
+
+
+def judge_multi(path, got, ref, q, what, term, first=0):
+    """assert_within, and next to the worst ratio beyond the term (0 where the term alone covers the error) the share of
+    the whole allowance that the run uses."""
+    note(path, ib.assert_within(got, ref, q, what, first=first, term=term))
+    note(path + ': share of the allowance', float(np.max(ib.allowance_share(got, ref, q, term, first))))
+
+
+def multi_setup(case, T=ib.T_MULTI):
+    sos, rate, fams, splits = ib.multi_design(case)
+    x = ib.families(fams, T, rate)
+    c = gh.ctx()
+    return sos, fams, x, c, gh.to_planar(c, x)
+
+
+@pytest.mark.parametrize('case,split', MULTI_SPLITS, ids=['%s as %s' % (case, splitname(split)) for case, split in MULTI_SPLITS])
+def test_envelope_multi(case, split):
+    """Every cascade and split in every segmentation, clamp off under the bound and its terms, clamp on bit for bit the
+    clamp of that."""
+    sos, fams, x, c, dx = multi_setup(case)
+    T, C = x.shape
+    ref, q = ib.envelope_case(sos, x)
+    capped(q, case)
+    term = ib.multi_term(sos, split, x)
+    plans = multi_plans(c, sos, split)
+    for seg, opts in SEGMENTATIONS:
+        with options(c, opts):
+            got = run_multi(c, plans, dx, T, C)
+            clamped = run_multi(c, plans, dx, T, C, clamp=True)
+        what = 'hipdsp_envelope_multi, %s as %s, %s' % (case, splitname(split), seg)
+        judge_multi('hipdsp_envelope_multi, %s as %s' % (case.split(' @')[0], splitname(split)), got, ref, q, what, term)
+        assert np.array_equal(clamped, ib.clamped(got)), what + ': the clamped run is not the clamp of the unclamped one'
+
+
+@pytest.mark.parametrize('case', ib.MULTI_SKIP)
+def test_envelope_multi_skip(case):
+    """`skip` up to, at and behind a tile border; the windows stay on the grid of sample 0."""
+    sos, fams, x, c, dx = multi_setup(case)
+    T, C = x.shape
+    ref, q = ib.envelope_case(sos, x)
+    capped(q, case)
+    split = ib.MULTI[case][5][0]
+    term = ib.multi_term(sos, split, x)
+    plans = multi_plans(c, sos, split)
+    for skip in ib.SKIPS:
+        for seg, opts in SEGMENTATIONS:
+            with options(c, opts):
+                got = run_multi(c, plans, dx, T, C, skip=skip)
+            what = 'hipdsp_envelope_multi, %s as %s, skip %d, %s' % (case, splitname(split), skip, seg)
+            judge_multi('hipdsp_envelope_multi, skip', got, ref[skip:], q, what, term[skip:], first=skip)
+
+
+@pytest.mark.parametrize('case', ib.MULTI_SKIP)
+def test_envelope_multi_pitches(case):
+    """Rows with slack on both sides and odd base offsets (4-byte alignment only): NaN in the slack of x must not be
+    read, the sentinel in the slack of y must stay."""
+    from audian_amd import hipdsp
+    sos, fams, x, c, _ = multi_setup(case)
+    T, C = x.shape
+    ref, q = ib.envelope_case(sos, x)
+    split = ib.MULTI[case][5][0]
+    term = ib.multi_term(sos, split, x)
+    plans = multi_plans(c, sos, split)
+    x_off, x_pitch, y_off = 3, T + 13, 5
+    host = np.full(x_off + C*x_pitch, np.nan, np.float32)
+    for ch in range(C):
+        host[x_off + ch*x_pitch:x_off + ch*x_pitch + T] = x[:, ch]
+    bx = hipdsp.DeviceArray.from_host(c, host)
+    dx = bx.view(x_off, (C*x_pitch,))
+    for skip in (0, 2047):
+        y_pitch = T - skip + 11
+        by = fresh(c, 1, y_off + C*y_pitch + 7)
+        sentinel = by.to_host()[0, 0]
+        dy = by.view(y_off, (C*y_pitch,))
+        hipdsp.envelope_multi(c, plans, dx, x_pitch, dy, y_pitch, C, T, skip, clamp=False)
+        raw = by.to_host()[0]
+        rows = raw[y_off:y_off + C*y_pitch].reshape(C, y_pitch)
+        what = 'hipdsp_envelope_multi, %s as %s, pitches %d / %d, skip %d' % (case, splitname(split), x_pitch, y_pitch, skip)
+        judge_multi('hipdsp_envelope_multi, pitches', rows[:, :T - skip].T, ref[skip:], q, what, term[skip:], first=skip)
+        slack = np.concatenate([raw[:y_off], rows[:, T - skip:].ravel(), raw[y_off + C*y_pitch:]])
+        assert np.all(slack.view(np.uint32) == sentinel.view(np.uint32)), what + ': written outside the rows'
+    assert np.array_equal(bx.to_host(), host, equal_nan=True)
+
+
+def test_envelope_multi_without_the_rectifier():
+    case = ib.MULTI_PLAIN
+    sos, fams, x, c, dx = multi_setup(case)
+    T, C = x.shape
+    ref, q = ib.envelope_case(sos, x, rectify=False)
+    capped(q, case + ', rectify 0')
+    split = ib.MULTI[case][5][0]
+    term = ib.multi_term(sos, split, x, rectify=False)
+    plans = multi_plans(c, sos, split)
+    for seg, opts in SEGMENTATIONS:
+        with options(c, opts):
+            got = run_multi(c, plans, dx, T, C, rectify=False, gain=123.0)         # (the gain belongs to the rectifier)
+        judge_multi('hipdsp_envelope_multi, rectify 0', got, ref, q,
+                    'hipdsp_envelope_multi, rectify 0, %s as %s, %s' % (case, splitname(split), seg), term)
+
+
+def test_envelope_multi_with_another_gain():
+    case, gain = ib.MULTI_GAIN
+    sos, fams, x, c, dx = multi_setup(case)
+    T, C = x.shape
+    ref, q = ib.envelope_case(sos, x, gain=gain)
+    capped(q, case + ', gain %g' % gain)
+    split = ib.MULTI[case][5][0]
+    term = ib.multi_term(sos, split, x, gain=gain)
+    plans = multi_plans(c, sos, split)
+    for seg, opts in SEGMENTATIONS:
+        with options(c, opts):
+            got = run_multi(c, plans, dx, T, C, gain=gain)
+        judge_multi('hipdsp_envelope_multi, gain %g' % gain, got, ref, q,
+                    'hipdsp_envelope_multi, gain %g, %s as %s, %s' % (gain, case, splitname(split), seg), term)
+
+
+def test_envelope_multi_and_the_single_plan_call():
+    """A four-section cascade as 2 + 2, as 1 + 1 + 1 + 1 and through hipdsp_envelope: one reference, each run with the
+    term of its own roundings (the single plan: the float32 tile between the passes)."""
+    from audian_amd import hipdsp
+    case = ib.MULTI_SINGLE
+    sos, fams, x, c, dx = multi_setup(case)
+    T, C = x.shape
+    ref, q = ib.envelope_case(sos, x)
+    capped(q, case)
+    for seg, opts in SEGMENTATIONS:
+        for split in ib.MULTI[case][5]:
+            with options(c, opts):
+                got = run_multi(c, multi_plans(c, sos, split), dx, T, C)
+            judge_multi('hipdsp_envelope_multi, %s as %s' % (case.split(' @')[0], splitname(split)), got, ref, q,
+                        'hipdsp_envelope_multi, %s as %s, %s' % (case, splitname(split), seg), ib.multi_term(sos, split, x))
+        with options(c, opts):
+            got = run_envelope(c, hipdsp.SosPlan(c, sos), dx, T, C)
+        judge_multi('hipdsp_envelope, 4 sections, 8 tiles', got, ref, q, 'hipdsp_envelope, %s, %s' % (case, seg), ib.between_term(sos, x))
+
+
+@pytest.mark.parametrize('case', ib.MULTI_SKIP)
+def test_envelope_multi_in_place(case):
+    """"x and y may overlap": y == x (skip 0 and skip > 0) and a y that starts inside the last row of x give the bits of
+    the run with separate buffers."""
+    from audian_amd import hipdsp
+    sos, fams, x, c, _ = multi_setup(case)
+    T, C = x.shape
+    split = ib.MULTI[case][5][0]
+    plans = multi_plans(c, sos, split)
+    planar = np.ascontiguousarray(x.T)
+    for skip in (0, 2049):
+        dx = hipdsp.DeviceArray.from_host(c, planar)
+        want = run_multi(c, plans, dx, T, C, skip=skip, clamp=True)
+        hipdsp.envelope_multi(c, plans, dx, T, dx, T, C, T, skip, clamp=True)
+        assert np.array_equal(dx.to_host()[:, :T - skip].T, want), (case, skip, 'y == x')
+        if skip:
+            assert np.array_equal(dx.to_host()[:, T - skip:], planar[:, T - skip:]), (case, skip, 'written behind the rows')
+        both = hipdsp.DeviceArray(c, (2*C*T,), np.float32)
+        dx, dy = both.view(0, (C, T)), both.view((C - 1)*T + 101, (C, T))
+        dx.copy_from_host(planar)
+        hipdsp.envelope_multi(c, plans, dx, T, dy, T - skip, C, T, skip, clamp=True)
+        got = dy.to_host().ravel()[:C*(T - skip)].reshape(C, T - skip).T
+        assert np.array_equal(got, want), (case, skip, 'y over the tail of x')
+
+
+POISON_T = 4*ib.TILE + 5
+
+
+@pytest.mark.parametrize('case', ib.MULTI_SKIP)
+def test_envelope_multi_non_finite_samples_stay_in_their_lane(case):
+    """NaN, +inf and -inf at sample 0, at T - 1, at a tile border of the extended trace's sweep, at one of the trace's
+    own and inside a tile, in the planner's segmentation and in one-tile segments: that lane is NaN everywhere, every
+    other lane keeps the bits of the clean run."""
+    from audian_amd import hipdsp
+    sos, fams, x, c, dx = multi_setup(case, POISON_T)
+    T, C = x.shape
+    split = ib.MULTI[case][5][0]
+    plans = multi_plans(c, sos, split)
+    lane = 1
+    others = [ch for ch in range(C) if ch != lane]
+    for seg, opts in (SEGMENTATIONS[2], SEGMENTATIONS[3]):
+        with options(c, opts):
+            clean = run_multi(c, plans, dx, T, C)
+            assert np.all(np.isfinite(clean))
+            for pos in (0, T - 1, ib.TILE - ib.padlen(sos), 2*ib.TILE, 5000):
+                for value in (np.nan, np.inf, -np.inf):
+                    bad = x.copy()
+                    bad[pos, lane] = value
+                    got = run_multi(c, plans, gh.to_planar(c, bad), T, C)
+                    what = (case, seg, pos, value)
+                    assert np.all(np.isnan(got[:, lane])), what
+                    assert np.array_equal(got[:, others], clean[:, others]), what
+
+
+def test_envelope_multi_edges():
+    """Eight sections, pad length 51: 51 frames raise like scipy, 52 run under the bound; skip == frames writes nothing."""
+    from audian_amd import hipdsp
+    case = ib.MULTI_EDGE
+    sos, rate, fams, splits = ib.multi_design(case)
+    split = splits[0]
+    edge = ib.padlen(sos)
+    assert len(sos) == 8 and edge == 51
+    c = gh.ctx()
+    plans = multi_plans(c, sos, split)
+    x = ib.families(fams, edge, rate)
+    dy = fresh(c, len(fams), edge)
+    with pytest.raises(ValueError, match='padlen'):
+        hipdsp.envelope_multi(c, plans, gh.to_planar(c, x), edge, dy, edge, len(fams), edge, 0)
+    T, C = edge + 1, len(fams)
+    x = ib.families(fams, T, rate)
+    ref, q = ib.envelope_case(sos, x)
+    capped(q, case + ', %d frames' % T)
+    ib.assert_in_range(ref, case + ', %d frames' % T)
+    dx = gh.to_planar(c, x)
+    for seg, opts in SEGMENTATIONS:
+        with options(c, opts):
+            got = run_multi(c, plans, dx, T, C)
+        judge_multi('hipdsp_envelope_multi, padlen + 1 frames', got, ref, q,
+                    'hipdsp_envelope_multi, %s, %d frames, %s' % (case, T, seg), ib.multi_term(sos, split, x))
+    dy = fresh(c, C, 8)
+    before = dy.to_host()
+    hipdsp.envelope_multi(c, plans, dx, T, dy, 8, C, T, T)
+    assert np.array_equal(dy.to_host().view(np.uint32), before.view(np.uint32)), 'skip == frames wrote something'
+
+
+def test_envelope_multi_sixteen_plans():
+    """The limit of the call: sixteen one-section plans (a band-pass of order 16 at its pad length + 1) run under the
+    bound, seventeen are refused."""
+    from audian_amd import hipdsp
+    from audian_amd.design import butter_sos
+    rate, fams, split = 48000.0, ib.HP_FAMILIES, (1,)*16
+    sos = butter_sos(16, (50.0, 4000.0), 'bandpass', rate)
+    assert len(sos) == 16
+    T, C = ib.padlen(sos) + 1, len(fams)
+    x = ib.families(fams, T, rate)
+    ref, q = ib.envelope_case(sos, x)
+    capped(q, 'bp16')
+    ib.assert_in_range(ref, 'bp16')
+    c = gh.ctx()
+    dx = gh.to_planar(c, x)
+    plans = multi_plans(c, sos, split)
+    got = run_multi(c, plans, dx, T, C)
+    judge_multi('hipdsp_envelope_multi, 16 plans', got, ref, q, 'hipdsp_envelope_multi, 16 plans', ib.multi_term(sos, split, x))
+    dy = fresh(c, C, T)
+    with pytest.raises(ValueError, match='n_plans'):
+        hipdsp.envelope_multi(c, plans + plans[:1], dx, T, dy, T, C, T, 0)
+    assert np.all(dy.to_host().view(np.uint32) == 0x7f7f7f7f)
+
+
 def test_zz_worst_per_path():
-    """The worst ratio e_w / (2^-24 r_w) of every path measured above (run with -s to see the table); with a
-    high-pass: of what is left beyond the extension term."""
+    """The worst ratio e_w / (2^-24 r_w) of every path measured above (run with -s to see the table); with a term: of
+    what is left beyond it, and for hipdsp_envelope_multi also the share of the whole allowance used."""
     if not WORST:
         print('\n(no path measured in this session)')
         return
-    lines = ['%-50s %s' % ('path', 'worst e_w / (2^-24 r_w)')]
+    lines = ['%-72s %s' % ('path', 'worst e_w / (2^-24 r_w)')]
     for path, worst in sorted(WORST.items()):
-        lines.append('%-50s %.4f' % (path, worst))
+        lines.append('%-72s %.4f' % (path, worst))
     print('\n' + '\n'.join(lines))

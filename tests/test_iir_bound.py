@@ -13,6 +13,11 @@
 4. Two wrong versions violate the bound: the cascade's state rounded to float32 at every tile border -- while still
    passing rel_err < 1e-4 on the same data, the gap this bound closes -- and eight-tile segments warmed up over one
    tile only, on the filter with the longest memory.
+5. hipdsp_envelope_multi (a cascade over several plans, float32 between them): every case of iir_bound.MULTI meets the
+   cap and the range at T_MULTI; the restatement of a five- and an eight-section cascade is the oracle's; the model of
+   the call with its 2P - 1 roundings lies inside the bound with iir_bound.handover_term (1 for 16); five wrong
+   versions of that model each fall outside it on at least one case, several of them under rel_err < 1e-4
+   (test_zz_multi_table prints the figures, run with -s).
 """
 
 import numpy as np
@@ -189,3 +194,152 @@ def test_a_one_tile_warm_up_is_caught():
     assert np.any(rho > 1.0 + ib.MARGIN*q)
     with pytest.raises(AssertionError):
         ib.assert_within(wrong, ref, q, case)
+
+
+# ---- hipdsp_envelope_multi ---------------------------------------------------------------------------------------------
+
+def multi_case(case):
+    sos, rate, fams, splits = ib.multi_design(case)
+    x = ib.families(fams, ib.T_MULTI, rate)
+    ref, run = ib.envelope_runs(sos, x)
+    return sos, fams, splits, x, ref, run
+
+
+@pytest.mark.parametrize('case', list(ib.MULTI))
+def test_multi_cases_meet_the_cap_and_the_range(case):
+    sos, fams, splits, x, ref, run = multi_case(case)
+    q = check_case(ref, run, '%s, T %d' % (case, ib.T_MULTI))
+    assert ib.has_highpass(sos) == (fams is ib.HP_FAMILIES)
+    assert all(sum(split) == len(sos) and max(split) <= 4 for split in splits)
+    if case == ib.MULTI_PLAIN:
+        ref, run = ib.envelope_runs(sos, x, rectify=False)
+        check_case(ref, run, case + ', rectify 0')
+    if case == ib.MULTI_GAIN[0]:
+        ref, run = ib.envelope_runs(sos, x, gain=ib.MULTI_GAIN[1])
+        check_case(ref, run, case + ', gain %g' % ib.MULTI_GAIN[1])
+    if case in ib.MULTI_SKIP:
+        assert ib.T_MULTI - max(ib.SKIPS) > ib.padlen(sos)
+
+
+@pytest.mark.parametrize('case', ['lp10 800 Hz @ 48 kHz', 'bp8 50-4000 Hz @ 48 kHz'])
+def test_multi_restatement_is_the_oracles(oracle, case):
+    """Five and eight sections: pad length, zi and sosfiltfilt of the whole cascade."""
+    sos, rate, fams, _ = ib.multi_design(case)
+    assert len(sos) == (5 if case.startswith('lp10') else 8)
+    assert ib.padlen(sos) == oracle.sosfiltfilt_edge(sos)
+    zi = oracle.sosfilt_zi(sos)
+    assert np.max(np.abs(ib.sosfilt_zi(sos, np.float64) - zi)) <= 1e-10*np.max(np.abs(zi))
+    x = ib.families(fams, 4096, rate)
+    want = oracle.sosfiltfilt(sos, (np.pi/2)*np.abs(x.astype(np.float64)))
+    assert peak_err(ib.sosfiltfilt(sos, x, np.float64, clamp=False), want) <= 1e-10
+    assert peak_err(ib.sosfiltfilt(sos, x, ib.LD, clamp=False), want) <= 1e-10
+
+
+def model_figures(case, _memo={}):
+    """{split: (the model's worst e_w / (2^-24 r_w), share of the allowance used, median and largest term / (2^-24 r_w))},
+    after asserting the model inside (1 + q) 2^-24 r_w + term for every split and lane."""
+    if case not in _memo:
+        sos, fams, splits, x, ref, run = multi_case(case)
+        q = ib.allowance(run, ref)
+        _, r = ib.window_stats(ref, ref)
+        ok = r > 0
+        rows = {'q': float(np.max(q))}
+        for split in splits:
+            what = '%s as %s' % (case, '+'.join(str(n) for n in split))
+            model = ib.multi_model(sos, split, x)
+            term = ib.multi_term(sos, split, x)
+            ib.assert_within(model, ref, q, what + ', the model', margin=1.0, term=term)
+            _, t = ib.window_stats(term, term)
+            size = np.asarray(t[ok]/(ib.ULP*r[ok]), dtype=np.float64)
+            rows[split] = (float(np.max(ib.ratios(model, ref))), float(np.max(ib.allowance_share(model, ref, q, term))),
+                           float(np.median(size)), float(np.max(size)))
+        _memo[case] = rows
+    return _memo[case]
+
+
+def figure_lines(case):
+    rows = model_figures(case)
+    return ['%-24s %-8s q %.1e  model %5.2f roundings, %3.0f %% of the allowance; term median %6.1f, largest %6.0f' % (
+        (case, '+'.join(str(n) for n in split), rows['q'], figures[0], 100*figures[1]) + figures[2:])
+        for split, figures in rows.items() if split != 'q']
+
+
+@pytest.mark.parametrize('case', list(ib.MULTI))
+def test_multi_model_lies_inside_the_bound(case):
+    """The call restated with its roundings, every split and lane: inside (1 + q) 2^-24 r_w + term (1 for 16); also
+    without the rectifier and with another gain."""
+    sos, fams, splits, x, ref, run = multi_case(case)
+    print('\n'.join(figure_lines(case)))
+    assert all(figures[1] <= 1.0 for split, figures in model_figures(case).items() if split != 'q')
+    split = splits[0]
+    if case == ib.MULTI_PLAIN:
+        ref, run = ib.envelope_runs(sos, x, rectify=False)
+        ib.assert_within(ib.multi_model(sos, split, x, rectify=False), ref, ib.allowance(run, ref), case + ', rectify 0',
+                         margin=1.0, term=ib.multi_term(sos, split, x, rectify=False))
+    if case == ib.MULTI_GAIN[0]:
+        gain = ib.MULTI_GAIN[1]
+        ref, run = ib.envelope_runs(sos, x, gain=gain)
+        ib.assert_within(ib.multi_model(sos, split, x, gain=gain), ref, ib.allowance(run, ref), case + ', gain %g' % gain,
+                         margin=1.0, term=ib.multi_term(sos, split, x, gain=gain))
+
+
+WRONG_CASES = [c for c in ib.MULTI if c != ib.MULTI_SINGLE]
+
+
+def wrong_figures(case, _memo={}):
+    """{wrong version: (per lane e_w / allowed under the bound the GPU tests apply, 16 and all; per lane rel_err)} on the
+    case's first split, after checking that assert_within says the same."""
+    if case not in _memo:
+        sos, fams, splits, x, ref, run = multi_case(case)
+        q = ib.allowance(run, ref)
+        split = splits[0]
+        term = ib.multi_term(sos, split, x)
+        ref64 = np.asarray(ref, dtype=np.float64)
+        rows = {}
+        for wrong in ib.MULTI_WRONG:
+            got = ib.multi_model(sos, split, x, wrong=wrong)
+            miss = ib.allowance_share(got, ref, q, term)
+            old = np.array([rel_err(got[:, c].astype(np.float64), ref64[:, c]) for c in range(x.shape[1])])
+            if np.max(miss) > 1.0:
+                with pytest.raises(AssertionError):
+                    ib.assert_within(got, ref, q, case, term=term)
+            else:
+                ib.assert_within(got, ref, q, case, term=term)
+            rows[wrong] = (miss, old)
+        _memo[case] = rows
+    return _memo[case]
+
+
+@pytest.mark.parametrize('case', WRONG_CASES)
+def test_multi_wrong_versions(case):
+    """Every wrong version of the model, per lane: by how much it misses the bound, and what rel_err makes of it.
+    Judged over all cases by test_zz_multi_table."""
+    for wrong, (miss, old) in wrong_figures(case).items():
+        print('%s, %s: e_w / allowed %s, rel_err %s' % (case, wrong, ' '.join('%.3g' % v for v in miss),
+                                                         ' '.join('%.2g' % v for v in old)))
+
+
+def test_zz_multi_table():
+    """The teeth of the multi-plan bound and the calibration's table (run with -s): every wrong version falls outside
+    the bound on at least one case, at least two of them on a lane that rel_err < 1e-4 lets through meanwhile; the
+    float32 state is caught on the 10-500 Hz band-pass and stays inside on the 800 Hz low-pass, where the designed
+    hand-over dominates."""
+    lines = [line for case in ib.MULTI for line in figure_lines(case)]
+    quiet = 0
+    worst = {}
+    for wrong in ib.MULTI_WRONG:
+        seen = {case: wrong_figures(case)[wrong] for case in WRONG_CASES}
+        worst[wrong] = {case: float(np.max(miss)) for case, (miss, _) in seen.items()}
+        caught = {c: m for c, m in worst[wrong].items() if m > 1.0}
+        inside = {c: m for c, m in worst[wrong].items() if m <= 1.0}
+        through = any(np.any((miss > 1.0) & (old < 1e-4)) for miss, old in seen.values())
+        quiet += through
+        lines.append('%s: caught on %s; inside on %s%s' % (
+            wrong, ', '.join('%s (%.3g)' % (c.split(' @')[0], m) for c, m in caught.items()) or 'nothing',
+            ', '.join('%s (%.2f)' % (c.split(' @')[0], m) for c, m in inside.items()) or 'nothing',
+            '; under rel_err < 1e-4 meanwhile' if through else ''))
+        assert caught, wrong
+    print('\n' + '\n'.join(lines))
+    assert quiet >= 2
+    assert worst['float32 state at tile borders']['lp10 800 Hz @ 48 kHz'] <= 1.0
+    assert worst['float32 state at tile borders']['bp5 10-500 Hz @ 48 kHz'] > 1.0
