@@ -387,7 +387,6 @@ int hipdsp_chain_forward(hipdsp_ctx *ctx, const hipdsp_sosplan *fplan, const hip
         rc = hipdsp_scratch(ctx, sizeof(double) * (size_t)ckpt_pitch * (size_t)channels, &work);
         if (rc != HIPDSP_OK) return rc;
     }
-    hd_note_sweep(ctx, gs.lead, gs.env0, frames, channels, SE);    // what a backward sweep (phase 2) must agree with
     a.c.in = x - gs.lead; a.c.yf = yf - gs.lead; a.c.ckpt = (double *)work;
     a.c.in_pitch = x_pitch; a.c.yf_pitch = yf_pitch; a.c.ckpt_pitch = ckpt_pitch;
     a.c.T = T; a.c.edge = edge; a.c.rectify = rectify; a.c.gain = rectify ? gain : 1.0;
@@ -453,9 +452,14 @@ int hipdsp_chain_forward(hipdsp_ctx *ctx, const hipdsp_sosplan *fplan, const hip
     fl.y = yf; fl.y_pitch = yf_pitch; fl.T = T; fl.skip = gs.lead;       // (sample p' of the sweep is yf[p' - lead])
     fl.psd = psd; fl.db = db_out; fl.psd_pitch = psd_pitch; fl.n_valid = n_valid;
     fl.F = (int)F; fl.nfft = nfft; fl.hop = hop; fl.frame_off = gs.frame_off;
-    if (SE == 0) return launch_flood(ctx, fl, channels);
-    return hd_launch_env_fix(ctx, eplan->dev, SE, (double *)work, ckpt_pitch, channels, a.c.n_seg, a.c.seg_len, n_tiles, &fl,
-                             (int)((gs.env0 - gs.env0 % TILE) / a.c.seg_len));
+    rc = SE == 0 ? launch_flood(ctx, fl, channels)
+                 : hd_launch_env_fix(ctx, eplan->dev, SE, (double *)work, ckpt_pitch, channels, a.c.n_seg, a.c.seg_len, n_tiles, &fl,
+                                     (int)((gs.env0 - gs.env0 % TILE) / a.c.seg_len));
+    if (rc != HIPDSP_OK) return rc;
+    // Only a sweep whose every launch went out has parked tile states: what a backward sweep (phase 2) must agree with.
+    // (hipdsp_scratch() above forgot the sweep before; a return on the way leaves the context without one.)
+    hd_note_sweep(ctx, gs.lead, gs.env0, frames, channels, SE);
+    return HIPDSP_OK;
 }
 
 int hipdsp_chain_backward(hipdsp_ctx *ctx, const hipdsp_sosplan *eplan, const float *yf, int64_t yf_pitch, float *env,

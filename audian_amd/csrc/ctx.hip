@@ -113,6 +113,7 @@ int hipdsp_ctx_create(int device, void *stream, hipdsp_ctx **out)
     ctx->graphs_alive = 0;
     ctx->seg_flags = nullptr;
     ctx->seg_flags_cap = 0;
+    ctx->scratch_fill = 0;
     {
         void *h = nullptr, *d = nullptr;
         hipError_t e = hipHostMalloc(&h, 64, hipHostMallocMapped);
@@ -240,6 +241,11 @@ int hipdsp_ctx_set_option(hipdsp_ctx *ctx, const char *name, long long value)
     if (strcmp(name, "chain_reserve_cus") == 0) {
         HD_REQUIRE(value >= 0 && value < ctx->n_cus, "chain_reserve_cus %lld not in [0, %d)", value, ctx->n_cus);
         ctx->chain_reserve_cus = (int)value;
+        return HIPDSP_OK;
+    }
+    if (strcmp(name, "scratch_fill") == 0) {          // tests: byte value - 1 over the scratch at every hand-out (0 = off)
+        HD_REQUIRE(value >= 0 && value <= 256, "scratch_fill %lld not in [0, 256]", value);
+        ctx->scratch_fill = (int)value;
         return HIPDSP_OK;
     }
     if (strcmp(name, "n_cus") == 0) {                 // tests: pretend a smaller chip (planning only)
@@ -639,6 +645,18 @@ int hd_device_fault(hipdsp_ctx *ctx)
     return HIPDSP_ERR_HIP;
 }
 
+// "scratch_fill" (tests): what a call is about to be handed holds byte value - 1 wherever the call does not write it.
+// One memset on the context's stream, in front of the call's kernels; never recorded into a capture.
+static int hd_fill_block(hipdsp_ctx *ctx, void *block, size_t bytes)
+{
+    if (block == nullptr || bytes == 0) return HIPDSP_OK;
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (ctx->stream) (void)hipStreamIsCapturing(ctx->stream, &st);
+    if (st != hipStreamCaptureStatusNone) return HIPDSP_OK;
+    HD_CHECK_HIP(hipMemsetAsync(block, ctx->scratch_fill - 1, bytes, ctx->stream));
+    return HIPDSP_OK;
+}
+
 int hd_seg_flags(hipdsp_ctx *ctx, size_t units, unsigned char **out)
 {
     if (units > ctx->seg_flags_cap) {
@@ -663,6 +681,10 @@ int hd_seg_flags(hipdsp_ctx *ctx, size_t units, unsigned char **out)
         HD_CHECK_HIP(e);
         ctx->seg_flags = (unsigned char *)f;
         ctx->seg_flags_cap = units;
+    }
+    if (ctx->scratch_fill) {
+        const int rc = hd_fill_block(ctx, ctx->seg_flags, ctx->seg_flags_cap);
+        if (rc != HIPDSP_OK) return rc;
     }
     *out = ctx->seg_flags;
     return HIPDSP_OK;
@@ -714,6 +736,10 @@ int hipdsp_scratch(hipdsp_ctx *ctx, size_t bytes, void **out)
         }
         HD_CHECK_HIP(e);
         ctx->scratch_bytes = bytes;
+    }
+    if (ctx->scratch_fill) {
+        const int rc = hd_fill_block(ctx, ctx->scratch, ctx->scratch_bytes);
+        if (rc != HIPDSP_OK) return rc;
     }
     *out = ctx->scratch;
     return HIPDSP_OK;

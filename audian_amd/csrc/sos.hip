@@ -978,7 +978,6 @@ int launch_env_ckpt(hipdsp_ctx *ctx, const SosPlanDev *fdev, const SosPlanDev *e
         fa.in_pitch = x_pitch; fa.yf_pitch = yf_pitch; fa.ckpt_pitch = ckpt_pitch;
         fa.T = frames; fa.edge = edge; fa.rectify = rectify; fa.gain = rectify ? gain : 1.0;
         fa.lead = gs.lead; fa.env0 = gs.env0;
-        hd_note_sweep(ctx, gs.lead, gs.env0, real_frames, channels, SE);
         // only the band-pass warms up; the envelope's states are handed over exactly (env_fix_kernel), which needs
         // a cascade that forgets (a plan that does not decay is never cut into segments)
         long long warm = warmF;
@@ -1020,6 +1019,9 @@ int launch_env_ckpt(hipdsp_ctx *ctx, const SosPlanDev *fdev, const SosPlanDev *e
         rc = launch_env_fix(ctx, edev, SE, (double *)work, ckpt_pitch, channels, fa.n_seg, fa.seg_len, n_tiles, &fl,
                             (int)((gs.env0 - gs.env0 % TILE) / fa.seg_len));
         if (rc != HIPDSP_OK) return rc;
+        // every launch of the forward sweep went out: only now are its tile states parked (hipdsp_scratch() forgot the
+        // sweep before it, so a return on the way leaves none for phase 2)
+        hd_note_sweep(ctx, gs.lead, gs.env0, real_frames, channels, SE);
     }
     if (phase == 1) return HIPDSP_OK;
     if (ctx->mid_event) HD_CHECK_HIP(hipEventRecord(ctx->mid_event, ctx->stream));

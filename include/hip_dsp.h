@@ -94,6 +94,11 @@ int hipdsp_ctx_set_max_segments(hipdsp_ctx *ctx, int max_segments);
  *                        32 = diagnostic build: db_out receives 16 clock sums per wave (tools/chain_stamps.py);
  *                        64 = no issue priorities at all; 128 (results unchanged) = FFT waves above IIR waves
  *                        only, without the progress words that keep the waves of a SIMD in step
+ *   "scratch_fill"       testing only (0 = off, the default): v in 1 ... 256 fills the context's whole scratch with
+ *                        byte v - 1 every time a call asks for it, and the segment flags of the IIR sweeps likewise,
+ *                        by one stream-ordered memset before the call's kernels (never the tile states a forward sweep
+ *                        parked for its backward sweep, and not while the stream is capturing).  Results must not
+ *                        depend on it at all, not even in rounding: what a call reads from the scratch it has written
  * Device-side faults: the waits between the waves of hipdsp_chain_forward's kernel are bounded; a wave
  * whose wait runs out writes a fault word owned by the context and ends the launch early.
  * hipdsp_ctx_synchronize, hipdsp_memcpy_d2h, hipdsp_event_elapsed_ms and the next

@@ -51,9 +51,9 @@ def family(name, rng, C, n):
 class Slab(object):
     """A host (C, frames) float32 array on the device with a base offset of 3 elements and pitch = frames + 7."""
 
-    def __init__(self, x, pitch_extra=7):
+    def __init__(self, x, pitch_extra=7, ctx=None):
         from audian_amd import hipdsp
-        self.ctx = gh.ctx()
+        self.ctx = gh.ctx() if ctx is None else ctx
         self.x = np.ascontiguousarray(x, dtype=np.float32)
         self.C, self.frames = self.x.shape
         self.pitch = self.frames + pitch_extra

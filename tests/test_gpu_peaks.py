@@ -60,9 +60,9 @@ class Slab(object):
     """A host (C, frames) float32 array on the device, `base` elements into its allocation, pitch = frames + 7; the
     elements around the rows are +inf: higher than everything, they must not be looked at."""
 
-    def __init__(self, x, base=3, pitch_extra=7):
+    def __init__(self, x, base=3, pitch_extra=7, ctx=None):
         from audian_amd import hipdsp
-        self.ctx = gh.ctx()
+        self.ctx = gh.ctx() if ctx is None else ctx
         self.x = np.ascontiguousarray(x, dtype=np.float32)
         self.C, self.frames = self.x.shape
         self.base, self.pitch = base, self.frames + pitch_extra

@@ -33,9 +33,9 @@ def test_constant():
 class Slab(object):
     """As test_gpu_regionspectra.Slab: base offset 3 elements, pitch = frames + 7."""
 
-    def __init__(self, x, pitch_extra=7):
+    def __init__(self, x, pitch_extra=7, ctx=None):
         from audian_amd import hipdsp
-        self.ctx = gh.ctx()
+        self.ctx = gh.ctx() if ctx is None else ctx
         self.x = np.ascontiguousarray(x, dtype=np.float32)
         self.C, self.frames = self.x.shape
         self.pitch = self.frames + pitch_extra
