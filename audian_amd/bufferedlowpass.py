@@ -1,0 +1,89 @@
+"""Zero-phase low-pass on the fly: the reference's ``lowpass_filter`` (songdetector.py:49-54), ``filtfilt(*butter(1,
+cutoff), source)``, as a derived trace at its source's rate -- on the power envelope with cutoff = 1/minduration it is
+the slow envelope the detector's thresholds and events run on (songdetector.py:755).  ``process()`` is one
+``hipdsp_envelope`` call without rectification, gain or clamp, i.e. plain ``sosfiltfilt``."""
+
+import numpy as np
+
+from .buffereddata import BufferedData, _covers, _subtract
+from .design import butter_sos
+
+
+class BufferedLowpass(BufferedData):
+    """``sosfiltfilt(butter(filter_order, cutoff), source)`` per channel, one second of pre-roll like BufferedEnvelope."""
+
+    def __init__(self, name='slow-envelope', source='power-envelope', cutoff=2.0, filter_order=1, panel='trace',
+                 color='#aa0000', lw_thin=2.5, lw_thick=4):
+        BufferedData.__init__(self, name, source, tbefore=1, panel=panel, panel_type='trace', color=color,
+                              lw_thin=lw_thin, lw_thick=lw_thick)
+        self.cutoff, self.filter_order, self.sos = cutoff, filter_order, None
+        self._plan = None
+        self._plan_key = None
+        self._design_key = None
+
+    def open(self, source):
+        BufferedData.open(self, source)
+        self.sos, self._design_key = None, None
+        self.update()
+
+    def update(self, cutoff=None):
+        """A new cut-off (None: as it is).  Recomputes this trace and what hangs below it, never the source."""
+        if cutoff is not None:
+            self.cutoff = cutoff
+        self._design()
+        self.recompute_all()
+
+    def _design(self):
+        """The low-pass at this trace's rate (which follows its source's: a power envelope may change its step); a design
+        scipy would reject leaves sos = None, i.e. a zero trace."""
+        key = (self.filter_order, self.cutoff, self.rate)
+        if key != self._design_key:
+            try:
+                self.sos = butter_sos(self.filter_order, self.cutoff, 'lowpass', self.rate)
+            except ValueError:
+                self.sos = None
+            self._design_key = key
+
+    def _device_plan(self, hipdsp):
+        key = self.sos.tobytes()
+        if self._plan is None:
+            self._plan = hipdsp.SosPlan(self.ctx, self.sos)
+        elif key != self._plan_key:
+            self._plan.set(self.sos)
+        self._plan_key = key
+        return self._plan
+
+    def process(self, source, dest, nbefore):
+        """dest = sosfiltfilt(sos, source, axis=0)[nbefore:]; zeros when the design failed.  Raises ValueError like scipy
+        when the slab is not longer than the pad length."""
+        from . import hipdsp
+        self._design()
+        if len(dest) != len(source) - nbefore:
+            raise ValueError(f'could not broadcast input array from shape ({len(source) - nbefore},) into shape '
+                             f'({len(dest)},)')
+        call = self._take_call(source, dest)
+        if len(dest) == 0:
+            return
+        src = self.source
+        if call is not None and isinstance(src, BufferedData) and src._dev is not None and \
+           _covers(src._dev_valid, call.soffset, call.soffset + call.snframes):
+            ddst, dpitch, is_mirror = self._device_dest(dest, call)
+            if self.sos is None:
+                hipdsp.envelope(self.ctx, None, None, 0, ddst, dpitch, self.channels, len(dest), 0)
+            else:
+                hipdsp.envelope(self.ctx, self._device_plan(hipdsp), src._dev.view(call.soffset, (1,)), src._pitch(), ddst,
+                                dpitch, self.channels, len(source), nbefore, rectify=False, gain=1.0, clamp=False)
+            self._finish_dest(dest, ddst, dpitch, is_mirror, call)
+            return
+        # no mirror to read (a plain host array, a host-only graph): numpy in float64
+        if self.sos is None:
+            dest[...] = 0.0
+        else:
+            from .refine import host_region_filtfilt
+            slab = np.asarray(source[:]).reshape(len(source), -1)
+            for c in range(slab.shape[1]):
+                dest[:, c] = host_region_filtfilt(slab[:, c], self.sos)[nbefore:]
+        if call is not None:
+            a, b = call.doffset, call.doffset + call.dnframes
+            self._dev_valid = _subtract(list(self._dev_valid), a, b)
+            self._stale = _subtract(list(self._stale), a, b)

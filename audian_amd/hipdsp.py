@@ -661,6 +661,29 @@ def region_filtfilt(ctx, x, x_pitch, y, y_pitch, channels, frames, regions, sos,
                                      int(bool(clamp))))
 
 
+POWER_ENVELOPE_CHUNK = 64               # samples per lane of hipdsp_power_envelope (csrc/powerenv.hip: PE_CHUNK), anchored at
+#                                         the first sample of a row's extended sequence
+POWER_ENVELOPE_TILE = 64*POWER_ENVELOPE_CHUNK     # samples per wave of it
+
+
+def power_envelope_scratch(channels, frames, n_sections, padlen):
+    """Bytes of context scratch one hipdsp_power_envelope call takes (the formula of include/hip_dsp.h)."""
+    tiles = -(-(int(frames) + 2*int(padlen))//POWER_ENVELOPE_TILE)
+    return int(channels)*(32*int(n_sections)*65*tiles + 4)
+
+
+def power_envelope(ctx, plan, x, x_pitch, channels, frames, y, y_pitch, first=0, step=1, n_out=None, gain=4.0, root=True):
+    """y[c, j] = float32(gain max(sosfiltfilt(plan, x[c]**2)[first + j step], 0)), j < n_out, and its root with `root`:
+    one hipdsp_power_envelope call (the reference's envelope(), songdetector.py:57-69, is the defaults with its step).
+    n_out None: every grid sample of the row.  Returns n_out."""
+    if n_out is None:
+        n_out = max(0, -(-(int(frames) - int(first))//int(step))) if step >= 1 else 0
+    _count('power_envelope')
+    check(lib.hipdsp_power_envelope(ctx.handle, _plan(plan), _p(x), int(x_pitch), int(channels), int(frames), int(first),
+                                    int(step), int(n_out), float(gain), int(bool(root)), _p(y), int(y_pitch)))
+    return int(n_out)
+
+
 def region_crossings(ctx, x, x_pitch, channels, frames, regions, thresholds, out=None):
     """n, number above, first above, one past the last above, max, argmax, 0, 0 of x[channel, start:stop] for every
     (channel, start, stop) of `regions` against the region's own threshold (hipdsp_region_crossings; positions in the

@@ -202,8 +202,9 @@ class TraceGraph(object):
         The buffers are moved as in detect_events so that the trace holds all events, then the trace computes
         (BufferedData.peak_freqs: on its device mirror when it has one, one call per nfft).  `step` decimates the
         trace before the spectra; None means 1, except on a BufferedEnvelope, which lives at the full rate here: there
-        it is max(1, round(rate / (10*envelope_cutoff))), the reference's envrate (songdetector.py:63-66).  Returns
-        one array of Hz per channel, aligned with events.onsets[channel]."""
+        it is max(1, round(rate / (10*envelope_cutoff))), the reference's envrate (songdetector.py:63-66).  A
+        BufferedPowerEnvelope already lives at the envelope rate: step 1.  Returns one array of Hz per channel, aligned
+        with events.onsets[channel]."""
         from .bufferedenvelope import BufferedEnvelope
         trace = self[events.trace_name if trace_name is None else trace_name]
         if step is None:
@@ -278,6 +279,22 @@ class TraceGraph(object):
             keep = rows[:, 2] >= 0
             out.append(rows[keep][:, 2:4].astype(np.int64))
         return Events(out, trace.rate, trace.name)
+
+    def detect_songs(self, env_name, slow_name, min_duration=0.5, peak_thresh=10.0, min_thresh_fac=1.0, t0=None, t1=None):
+        """The reference's song detector behind its envelope (main(), songdetector.py:757-767) as one call over the
+        methods above: histogram thresholds of the slow envelope `slow_name` (a BufferedLowpass of the envelope at 1 /
+        min_duration), its events with min_gap = min_duration = `min_duration`, the pulse rate of every event on the
+        envelope `env_name` (a BufferedPowerEnvelope; spectral peaks of at least `peak_thresh` dB prominence), the
+        cleaning of those rates and the events' borders again from local thresholds on the envelope.  No arithmetic of
+        its own.  Returns (events, freqs, thresholds): the refined Events (frames of the envelope), the cleaned rates per
+        channel (aligned with the events the refinement was given) and the thresholds per channel."""
+        thresholds = self.event_thresholds(slow_name, 0.0, t0, t1, method='histogram')
+        events = self.detect_events(slow_name, thresholds, min_gap=min_duration, min_duration=min_duration, t0=t0, t1=t1)
+        freqs = self.event_peak_freqs(events, env_name, thresh=peak_thresh)
+        events, freqs = self.clean_event_freqs(events, freqs)
+        events = self.refine_events(events, freqs, thresholds, trace_name=env_name, min_duration=min_duration,
+                                    min_thresh_fac=min_thresh_fac)
+        return events, freqs, thresholds
 
     @staticmethod
     def mark_peaks(analyzer, name, peaks):

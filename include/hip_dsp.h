@@ -963,6 +963,53 @@ int hipdsp_region_filtfilt(hipdsp_ctx *ctx, const float *x, int64_t x_pitch, flo
 int hipdsp_region_crossings(hipdsp_ctx *ctx, const float *x, int64_t x_pitch, int64_t channels, int64_t frames,
                             const int64_t *host_regions, const double *host_thresholds, int64_t n_regions, double *out);
 
+/* The power envelope at the envelope rate: the first step of the reference's song detector, envelope()
+ * (songdetector.py:57-69) -- the squares of a band-passed trace, a zero-phase low-pass of them, every step-th sample, the
+ * clamp at zero and the root -- in one call that never writes anything at full rate.
+ * x is planar float32: `channels` rows of `frames` valid elements, x_pitch apart; y: `channels` rows of n_out elements,
+ * y_pitch apart.  For one row v and the plan's table sos (one or two sections):
+ *   u    = float64(v)**2                                        exact
+ *   f    = scipy.signal.sosfiltfilt(sos, u)                     default odd extension OF u by the default padlen, forward
+ *                                                               pass from sosfilt_zi * ext[0], reversal, forward pass from
+ *                                                               sosfilt_zi * (its first sample), reversal, trim
+ *   p[j] = float32(gain * max(f[first + j step], 0)), j < n_out the product in float64, ONE rounding
+ *   y[j] = p[j] (root == 0), the correctly rounded float32 square root of p[j] (root != 0)
+ * tests/power_envelope_definition.py restates it.  The reference's envelope(data, rate, freq) is root = 1, gain = 4
+ * (sqrt(2 f) sqrt(2) = 2 sqrt(f)), first = 0, step = round(rate / min(10 freq, rate)), n_out = ceil(frames / step), with the
+ * plan of butter(1, freq) as ONE section with b2 = a2 = 0 (padlen 6: scipy.signal.filtfilt(b, a, u)); its edata[::step] is
+ * root = 0, gain = 2.  tests/golden/power_envelope.npz pins both to the reference's own function.
+ * Errors, all decided on the host before anything is launched or written:
+ *   HIPDSP_ERR_TOO_SHORT    frames <= padlen (scipy raises ValueError).
+ *   HIPDSP_ERR_UNSUPPORTED  a plan of more than two sections; more than 65535 channels or 2^40 frames.
+ *   HIPDSP_ERR_INVALID      step < 1; first < 0; first + (n_out - 1) step >= frames with n_out > 0; a gain that is not
+ *                           finite or <= 0; a NULL ctx or plan (or a plan never set); negative sizes; x_pitch < frames or
+ *                           y_pitch < n_out; misaligned pointers; y overlapping x; a stream capture in progress (the call
+ *                           sizes its scratch itself).
+ * n_out == 0 or channels == 0 writes nothing.  Nothing outside y[c y_pitch + j], j < n_out, is written.
+ * Non-finite samples: a row that holds a NaN or an infinity comes out NaN in every element; other rows keep their bits.
+ * (For infinities scipy gives NaN or infinities depending on the filter, as in hipdsp_region_filtfilt.)
+ * Accuracy: squares, extension, coefficients, state, every hand-over and the forward output that feeds the backward pass
+ * are float64; one rounding to float32 at the store, then the root.  The contract is the one of tests/iir_bound.py without
+ * its extension_term and between_term: with root = 0, gain = 1, step = 1, e_w <= (1 + 16 q) 2^-24 r_w for every window of 64
+ * samples, q the case's allowance.  There is no warm-up: where the extended sequence is cut the state is handed over
+ * exactly, state_out = A^L state_in + (the zero-state end state of the L samples), the powers of A computed on the host
+ * (squared in long double, each rounded once).  hipdsp_ctx_set_max_segments has nothing to reach: rows are not cut into
+ * segments that could start anywhere but at the row's own extension.
+ * Work (csrc/powerenv.hip): the extended sequence of a row (E = frames + 2 padlen samples) is cut into chunks of 64 samples
+ * counted from its first sample, 64 consecutive chunks are the tile of one wave.  Three sweeps over x and two carries: every
+ * chunk's zero-state end state and a scan over the tile's lanes; one wave per row handing the tiles' states on, 64 tiles
+ * per step; every chunk's forward output again from its true state, kept in registers, run backwards from zero state and
+ * scanned; the backward hand-over; the same again from the true states, writing the samples on the grid.  12 bytes read
+ * per sample, 4 / step written.  Uses the context scratch: 32 S bytes per chunk slot (64 per tile) and per tile plus 4 per
+ * row, S the number of sections -- S / 2 bytes per sample; like every call that uses the scratch, not between phase 1 and
+ * phase 2 of hipdsp_sosfilt_envelope.
+ * Determinism: no atomics.  The grid is anchored at the row's own extended sequence and sized by constants: a row's bytes
+ * depend on the row, the plan and (first, step, n_out, gain, root) alone, and the same call gives the same bytes twice.
+ * Index arithmetic is 64-bit; rows start at any 4-byte address. */
+int hipdsp_power_envelope(hipdsp_ctx *ctx, const hipdsp_sosplan *plan, const float *x, int64_t x_pitch,
+                          int64_t channels, int64_t frames, int64_t first, int64_t step, int64_t n_out,
+                          double gain, int root, float *y, int64_t y_pitch);
+
 /* ---- multi-GPU exchange ---------------------------------------- */
 
 /* One process per GPU, channels sharded in contiguous blocks of the planar layout, so

@@ -244,6 +244,20 @@ for b in builds:
     logs[b['name']].append(f'{"hipdsp_region_crossings, 10 regions of 7 s per channel":78s} {ms:8.3f} ms {4.0*len(table)*n7/ms/1e6:7.0f} GB/s')
     if b is builds[-1]:
         print(logs[b['name']][-1], flush=True)
+# ---- hipdsp_power_envelope: the filtered buffer to the song detector's envelope at the envelope rate, first-order low-pass at
+# 500 Hz, every 19th sample, with the root (tools/power_envelope_bench.py has the route through hipdsp_envelope + hipdsp_stride_copy)
+for b in builds:
+    h, ctx = b['h'], b['ctx']
+    if not hasattr(h.lib, 'hipdsp_power_envelope'):
+        continue
+    n_out = -(-T//19)
+    plan = h.SosPlan(ctx, b['design'].butter_sos(1, 500.0, 'lowpass', rate))
+    ms = min(timed(b, lambda: h.power_envelope(ctx, plan, b['buf']['df'], T, C, T, b['buf']['ds'], n_out, 0, 19, n_out, 4.0, True), 3)
+             for _ in range(rounds))
+    ctx.synchronize()
+    logs[b['name']].append(f'{"hipdsp_power_envelope, low-pass of 1 section at 500 Hz, step 19, root":78s} {ms:8.3f} ms {(12.0*S + 4.0*C*n_out)/ms/1e6:7.0f} GB/s')
+    if b is builds[-1]:
+        print(logs[b['name']][-1], flush=True)
 prefix = os.environ.get('OUT_PREFIX')
 if prefix:
     for name, lines in logs.items():
