@@ -349,11 +349,11 @@ __global__ __launch_bounds__(64 * WPB) void sos_ckpt_kernel(const SosPlanDev *__
 // Exact state hand-over between the time segments of the envelope's forward sweep.  After the sweep
 // the slot of segment k's first tile (k >= 1) holds e_(k-1), the state segment k-1 ended with having started from
 // zero (segment 0: from the true initial state), and the other slots hold zero-state tile states.  With
-// P = A^segment the true state entering segment k is S_k = e_(k-1) + P S_(k-1) = sum_j P^j e_(k-1-j), cut off
-// where ||P^j|| < 2^-60 (the plan's warm-up length says where), and the true state entering tile m of segment k is
-// its zero-state one + A^(TILE m) S_k -- added for the tiles of the warm-up length only, beyond which it is below
-// float64 rounding.  One block per channel; segments are taken from the last to the first in chunks of the block
-// size so that every e_k is read before it is overwritten with S_(k+1).
+// P = A^segment (applied tile by tile, see below) the true state entering segment k is S_k = e_(k-1) + P S_(k-1) =
+// sum_j P^j e_(k-1-j), cut off where ||P^j|| < 2^-60 (the plan's warm-up length says where), and the true state
+// entering tile m of segment k is its zero-state one + A^(TILE m) S_k -- added for the tiles of the warm-up length
+// only, beyond which it is below float64 rounding.  One block per channel; segments are taken from the last to the
+// first in chunks of the block size so that every e_k is read before it is overwritten with S_(k+1).
 // Non-finite input (FloodArgs): the block first overwrites what the band-pass segments behind a non-finite one wrote,
 // and if any segment's envelope state ended non-finite it leaves NaN in slot n_tiles for the backward sweep.
 template <int SE>
@@ -381,51 +381,20 @@ __global__ __launch_bounds__(256) void env_fix_kernel(const SosPlanDev *__restri
         if (any_bad && threadIdx.x == 0) ckpt[n_tiles * D] = __builtin_nan("");
         __syncthreads();
     }
-    double AT[D][D], P[D][D];
+    // P S is formed as seg_tiles products with A^TILE, never with a P = (A^TILE)^seg_tiles multiplied out in float64: the
+    // state transition of a slow low-pass is far from normal (20 Hz at 96 kHz: entries of A^TILE around 154 against
+    // eigenvalues of 0.15), every matrix product in float64 loses that factor of relative accuracy, and a P of two to five
+    // tiles put errors of 3e-7 into the states behind a loud passage (25 float32 roundings in the envelope there;
+    // tests/test_gpu_iir_accuracy.py: test_warmup_fused).  A segment longer than the warm-up hands nothing on beyond its
+    // own end state: ||A^(TILE seg_tiles)|| < 2^-60.
+    double AT[D][D];
 #pragma unroll
     for (int r = 0; r < D; r++)
 #pragma unroll
-        for (int c = 0; c < D; c++) { AT[r][c] = P0->AT[r * D + c]; P[r][c] = r == c ? 1.0 : 0.0; }
-    {   // P = AT^seg_tiles by binary exponentiation
-        double Q[D][D];
-#pragma unroll
-        for (int r = 0; r < D; r++)
-#pragma unroll
-            for (int c = 0; c < D; c++) Q[r][c] = AT[r][c];
-        for (long long e = seg_tiles; e > 0; e >>= 1) {
-            double t[D][D];
-            if (e & 1) {
-#pragma unroll
-                for (int r = 0; r < D; r++)
-#pragma unroll
-                    for (int c = 0; c < D; c++) {
-                        double acc = 0.0;
-#pragma unroll
-                        for (int k = 0; k < D; k++) acc = fma(P[r][k], Q[k][c], acc);
-                        t[r][c] = acc;
-                    }
-#pragma unroll
-                for (int r = 0; r < D; r++)
-#pragma unroll
-                    for (int c = 0; c < D; c++) P[r][c] = t[r][c];
-            }
-#pragma unroll
-            for (int r = 0; r < D; r++)
-#pragma unroll
-                for (int c = 0; c < D; c++) {
-                    double acc = 0.0;
-#pragma unroll
-                    for (int k = 0; k < D; k++) acc = fma(Q[r][k], Q[k][c], acc);
-                    t[r][c] = acc;
-                }
-#pragma unroll
-            for (int r = 0; r < D; r++)
-#pragma unroll
-                for (int c = 0; c < D; c++) Q[r][c] = t[r][c];
-        }
-    }
+        for (int c = 0; c < D; c++) AT[r][c] = P0->AT[r * D + c];
     const long long warm_tiles = P0->warm / TILE;                  // ||A^(TILE warm_tiles)|| < 2^-60
     const long long terms = (warm_tiles + seg_tiles - 1) / seg_tiles + 1;
+    const long long steps = seg_tiles <= warm_tiles ? seg_tiles : 0;    // products with A^TILE per P S; 0: P S is dropped
     for (long long k_hi = n_seg - 1; k_hi >= first_seg + 1; k_hi -= blockDim.x) {
         const long long k = k_hi - threadIdx.x;
         double S[D];
@@ -437,16 +406,24 @@ __global__ __launch_bounds__(256) void env_fix_kernel(const SosPlanDev *__restri
             if (j < first_seg) j = first_seg;
             for (; j < k; j++) {
                 const double *e = ckpt + (j + 1) * seg_tiles * D;
-                double t[D];
+                if (steps == 0) {
 #pragma unroll
-                for (int r = 0; r < D; r++) {
-                    double acc = e[r];
+                    for (int r = 0; r < D; r++) S[r] = 0.0;
+                }
+                for (long long m = 0; m < steps; m++) {
+                    double t[D];
 #pragma unroll
-                    for (int c = 0; c < D; c++) acc = fma(P[r][c], S[c], acc);
-                    t[r] = acc;
+                    for (int r = 0; r < D; r++) {
+                        double acc = 0.0;
+#pragma unroll
+                        for (int c = 0; c < D; c++) acc = fma(AT[r][c], S[c], acc);
+                        t[r] = acc;
+                    }
+#pragma unroll
+                    for (int r = 0; r < D; r++) S[r] = t[r];
                 }
 #pragma unroll
-                for (int r = 0; r < D; r++) S[r] = t[r];
+                for (int r = 0; r < D; r++) S[r] += e[r];
             }
         }
         __syncthreads();

@@ -289,6 +289,66 @@ def wrong_one_tile_warmup(sos, x, tiles=8):
     return y
 
 
+# ---- warm-ups that start inside the trace -----------------------------------------------------------------------------
+# A segment of a sweep starts from zero state `warm` samples before its range (sos_plan.hip: the smallest multiple of the
+# tile with ||A^warm|| < 2^-60): 26 tiles for the 20 Hz low-pass, 15 for the 100 Hz high-pass at 192 kHz.  At T_LONG (17
+# tiles) every such warm-up is clipped at the start of the trace, which is exact.  The rows below are long enough for a
+# segment to start from zero state in mid-trace: the third of three segments of 64 tiles starts at tile 44 and warms up
+# from tile 18.  The forward sweep of a band-pass (hipdsp_sosfilt, the fused sweeps) cuts off the past, and `stepdown`
+# shows it (quiet windows behind a loud passage); the backward sweep of an envelope cuts off the future, and `stepup`
+# shows it.  (The envelope's forward sweep hands its states over exactly and has no warm-up.)
+
+WARM_FAMILIES = ('stepdown', 'stepup', 'offset', 'burst')
+WARM_BANDPASS = 'hp3 100 Hz @ 192 kHz'          # BANDPASSES; 2 sections, warm-up 15 tiles; q at most 2.2e-3 at T_WARM
+WARM_ENVELOPE = 'lp2 20 Hz @ 96 kHz'            # ENVELOPES; 1 section, warm-up 26 tiles; q at most 5.3e-3 (forward pass)
+WARM_FUSED = 'bp2 300-3000 Hz @ 96 kHz'         # the band-pass in front of WARM_ENVELOPE in the fused launches
+T_WARM = {WARM_BANDPASS: 48*TILE + 5, WARM_ENVELOPE: 64*TILE + 5}
+WARM_TILES = {WARM_BANDPASS: 15, WARM_ENVELOPE: 26}       # what hipdsp_sos_plan_host gives (test_iir_bound.py asserts it)
+
+
+def segment_starts(n_tiles, seg_tiles):
+    """The first tile of every segment of a sweep over n_tiles tiles in segments of seg_tiles (in the sweep's order: a
+    backward sweep counts its tiles from the end of the extended trace)."""
+    return list(range(0, n_tiles, seg_tiles))
+
+
+def cut_warmups(n_tiles, seg_tiles, warm_tiles):
+    """The segments (first tile, first tile of the warm-up) whose warm-up starts inside the trace, at least one tile
+    from its start: the ones that run from zero state in place of history."""
+    return [(t, t - warm_tiles) for t in segment_starts(n_tiles, seg_tiles) if t - warm_tiles >= 1]
+
+
+def segmented_sosfilt(sos, x, warm_tiles, segments=3, zi=None, lead=0):
+    """The float64 run of sosfilt(sos, x) cut into `segments` segments of whole tiles, every one started from zero state
+    warm_tiles tiles before its range (from `zi` where that is the start of x).  `lead`: the tile grid starts that many
+    samples in front of x (a backward sweep's ragged first tile).  A model for the calibration, never a reference."""
+    x = np.asarray(x)
+    n_tiles = -(-(len(x) + lead)//TILE)
+    seg = -(-n_tiles//segments)*TILE
+    y = np.empty(x.shape, np.float64)
+    for lo in range(0, n_tiles*TILE, seg):
+        a, b = max(lo - lead, 0), min(lo + seg - lead, len(x))
+        start = max(lo - warm_tiles*TILE - lead, 0)
+        y[a:b] = sosfilt(sos, x[start:b], np.float64, zi=zi if start == 0 else None)[a - start:]
+    return y
+
+
+def segmented_envelope(sos, x, warm_tiles, segments=3, gain=GAIN):
+    """The float64 envelope of x, unclamped, as the sweeps cut it: the right extension formed in float32, the forward
+    pass whole (its states are handed over exactly), the backward pass over the trace and its right extension in
+    `segments` segments of whole tiles counted from the end, every one started from zero state warm_tiles tiles behind
+    its range.  A model for the calibration, never a reference."""
+    x = np.asarray(x)
+    T, edge = len(x), padlen(sos)
+    r = np.abs(x)
+    u = gain*r.astype(np.float64)
+    ext = np.concatenate([2*u[0] - u[edge:0:-1], u, gain*_ext32(r, edge)[1].astype(np.float64)])
+    zi = sosfilt_zi(sos, np.float64)
+    y = sosfilt(sos, ext, np.float64, zi=zi[:, :, None]*ext[0][None, None, :])
+    back = segmented_sosfilt(sos, y[::-1], warm_tiles, segments, zi=zi[:, :, None]*y[-1][None, None, :], lead=-(T + edge) % TILE)
+    return back[::-1][edge:edge + T]
+
+
 # ---- the metric -------------------------------------------------------------------------------------------------
 
 def window_stats(got, ref, first=0):

@@ -121,3 +121,184 @@ def host_power_envelope(sos, slab, first=0, step=1, n_out=None, gain=4.0, root=T
     """audian_amd.bufferedpowerenvelope.power_envelope_host, for the tests that compare with it."""
     from audian_amd.bufferedpowerenvelope import power_envelope_host
     return power_envelope_host(sos, slab, first, step, n_out, gain, root)
+
+
+# ---- rows longer than the filter's memory: the hand-over over chunks, tiles and blocks of 64 tiles -----------------------
+# csrc/powerenv.hip cuts the extended sequence (E = frames + 2 padlen) into chunks of 64 samples, tiles of 64 chunks and, in
+# pe_carry, blocks of 64 tiles, and hands the state over with the powers P[b] = A^(64 * 2^b): P[0 ... 5] between the chunks of
+# a tile, P[6 ... 11] between the tiles of a block, P[12] from block to block.  T_CASE (4 tiles) applies P[0 ... 7] only and
+# runs pe_carry's loop once.  The rows below reach the rest.
+
+CHUNK, TILE, BLOCK = 64, 4096, 64
+POWERS = 13
+
+# One section, tau = 15279 samples: A^(64 tiles) = 3.5e-8.  130 tiles and 5 samples, 131 tiles of the extended sequence: the
+# third step of pe_carry's loop (tiles 128 ... 130 forward, 2 ... 0 backward) is the first that consumes P[12] and the only
+# ragged one.  `stepdown` leaves quiet windows 96 tiles and more behind the loud quarter for the forward carry, `stepup` quiet
+# windows 63 tiles and more in front of the loud half for the backward carry.
+LONG = 'lp1 1 Hz @ 96 kHz'
+T_ROW = 130*TILE + 5
+LONG_FAMILIES = ('stepdown', 'stepup')
+
+# Two sections.  Of the order-3 and order-4 Butterworth low-passes at 48 kHz with a cut-off in whole Hz this is the one with
+# the longest memory (slowest pole pair at 4 Hz, tau = 1910 samples) whose q stays under Q_CAP = 0.0156 on the four families at
+# the longest row below: 0.0116, against 0.018 for lp3 7 Hz, 0.025 for lp3 6 Hz and 0.024 for lp4 10 Hz (slowest pair at 3.8
+# Hz); lp4 12 Hz meets the cap (0.0103) with a shorter memory (4.6 Hz).  The entering state of tile 2^b + 1 is the first that
+# P[6 + b] reaches (pe_scan adds P[6 + b] z_(r - 2^b) to z_r, and z_r enters tile r + 1), so the rows have 6, 10 and 18 tiles:
+# E = frames + 2 padlen one before a multiple of 4096 (the last tile of 4095 samples), on one, and one behind (the last tile
+# of one sample).  P[11] and P[12] are out of a two-section case's reach under the cap: max |P[11]| = 3.3e-24, max |P[12]| =
+# 4.5e-54 for this filter, against the 2^-36 that assert_in_range leaves between a row's loudest and quietest window.
+MIDDLE = 'lp3 8 Hz @ 48 kHz'
+MIDDLE_E = (6*TILE - 1, 10*TILE, 17*TILE + 1)
+
+LONG_FILTERS = {
+    LONG: (1, 1.0, 'lowpass', 96000.0, LONG_FAMILIES),                     # 1, 6
+    MIDDLE: (3, 8.0, 'lowpass', 48000.0, FAMILIES),                        # 2, 12
+}
+
+MUTATIONS = tuple('P[%d] = 0' % b for b in range(POWERS)) + tuple('P[%d] = P[%d]' % (b, b - 1) for b in range(1, POWERS)) + \
+    ('hand-over without P[12] s', 'downward blocks from the wrong end')
+
+
+def long_design(name):
+    """(sos, rate, families) of a case of LONG_FILTERS."""
+    return ib.design(name, LONG_FILTERS)
+
+
+def long_rows(name):
+    """The row lengths (frames) of a case of LONG_FILTERS."""
+    if name == LONG:
+        return (T_ROW,)
+    edge = ib.padlen(long_design(name)[0])
+    return tuple(E - 2*edge for E in MIDDLE_E)
+
+
+def tiles_of(sos, frames):
+    """How many tiles the extended sequence of a row has."""
+    return -(-(frames + 2*ib.padlen(sos))//TILE)
+
+
+def powers_reached(tiles):
+    """The b whose P[b] reaches a result of a row of `tiles` tiles: 0 ... 5 inside a tile; 6 + b from 2^b + 2 tiles on,
+    b <= 5; 12 from 129 tiles on (the third step of pe_carry's loop)."""
+    return [b for b in range(POWERS) if b < 6 or (b < 12 and tiles >= (1 << (b - 6)) + 2) or (b == 12 and tiles > 2*BLOCK)]
+
+
+def _emu_step(coef, z, v):
+    """One sample of the cascade (direct form II transposed) for the states z (2 S, ...) in place; the output."""
+    for s, (b0, b1, b2, a1, a2) in enumerate(coef):
+        o = b0*v + z[2*s]
+        z[2*s] = (b1*v - a1*o) + z[2*s + 1]
+        z[2*s + 1] = b2*v - a2*o
+        v = o
+    return v
+
+
+def transition_powers(sos):
+    """P[b] = A^(64 * 2^b), b = 0 ... 12, (13, 2 S, 2 S) float64: the cascade's state transition at zero input, squared
+    in longdouble and each power rounded once (pe_powers)."""
+    coef = ib._coef(sos, LD)
+    n = 2*len(coef)
+    z = np.eye(n, dtype=LD)                                 # column j: one step from the unit state e_j
+    _emu_step(coef, z, np.zeros(n, LD))
+    A = z
+    P = np.empty((POWERS, n, n))
+    for sq in range(1, 6 + POWERS):
+        A = A @ A
+        if sq >= 6:
+            P[sq - 6] = A.astype(np.float64)
+    return P
+
+
+def _emu_scan(P, base, z):
+    """pe_scan: z (n, groups, 64, lanes), rank r <- sum over m <= r of A^(64 2^base (r - m)) z_m, in six doubling steps."""
+    for b in range(6):
+        d = 1 << b
+        z[:, :, d:] = z[:, :, d:] + np.einsum('ij,jgrc->igrc', P[base + b], z[:, :, :-d])
+    return z
+
+
+def _emu_advance(P, base, s):
+    """pe_advance: s (n, groups, lanes) -> (n, groups, 64, lanes), rank r gets A^(64 2^base r) s by the bits of r."""
+    e = np.repeat(s[:, :, None, :], 64, axis=2)
+    rank = np.arange(64)
+    for b in range(6):
+        on = ((rank >> b) & 1) == 1
+        e[:, :, on] = np.einsum('ij,jgrc->igrc', P[base + b], e[:, :, on])
+    return e
+
+
+def _emu_pass(coef, P, w, at, state, mutation, down):
+    """One pass of csrc/powerenv.hip over w ((tiles * 4096, lanes) float64, in the pass's order, zeros where the grid
+    reaches beyond the sequence) in float64: chunks from zero state, the scan over a tile's chunks, pe_carry over blocks
+    of 64 tiles, the chunks again from their entering states.  `state` (2 S, lanes) joins the cascade's state in front of
+    sample `at` (scipy's zi times the pass's first sample)."""
+    n, lanes = 2*len(coef), w.shape[1]
+    chunks = len(w)//CHUNK
+    tiles = chunks//64
+    wc = w.reshape(chunks, CHUNK, lanes)
+
+    def run(z, keep):
+        y = np.empty((chunks, CHUNK, lanes)) if keep else None
+        for i in range(CHUNK):
+            if i == at % CHUNK:
+                z[:, at//CHUNK] += state
+            o = _emu_step(coef, z, wc[:, i])
+            if keep:
+                y[:, i] = o
+        return y
+
+    z = np.zeros((n, chunks, lanes))
+    run(z, False)
+    v = _emu_scan(P, 0, z.reshape(n, tiles, 64, lanes))    # what the tile adds to the state behind chunk l
+    # pe_carry: blocks of 64 tiles from the pass's first tile (for the backward pass the row's last one)
+    lead = 0
+    if down and mutation == 'downward blocks from the wrong end':
+        lead = -tiles % BLOCK                               # the blocks of the forward carry: the ragged one comes first
+    blocks = -(-(lead + tiles)//BLOCK)
+    sums = np.zeros((n, blocks*BLOCK, lanes))
+    first = 0
+    if lead:                                                # first block: the ragged one, its tiles in lanes 0 ...
+        first = tiles % BLOCK
+        sums[:, :first] = v[:, :first, 63]
+        sums[:, BLOCK:BLOCK + tiles - first] = v[:, first:, 63]
+    else:
+        sums[:, :tiles] = v[:, :, 63]
+    zt = _emu_scan(P, 6, sums.reshape(n, blocks, 64, lanes).copy())
+    s = np.zeros((n, lanes))
+    enter = np.empty((n, blocks, 64, lanes))
+    for k in range(blocks):
+        e = _emu_advance(P, 6, s[:, None, :])[:, 0]
+        e[:, 1:] += zt[:, k, :-1]
+        enter[:, k] = e
+        s = zt[:, k, 63] + (0.0 if mutation == 'hand-over without P[12] s' else P[12] @ s)
+    enter = enter.reshape(n, blocks*BLOCK, lanes)
+    enter = np.concatenate([enter[:, :first], enter[:, BLOCK:BLOCK + tiles - first]], axis=1) if lead else enter[:, :tiles]
+    z = _emu_advance(P, 0, enter)                           # A^(64 l) s_t + v_(l-1)
+    z[:, :, 1:] += v[:, :, :-1]
+    return run(np.ascontiguousarray(z.reshape(n, chunks, lanes)), True).reshape(chunks*CHUNK, lanes)
+
+
+def carry_emulation(sos, x, mutation=None):
+    """f of the definition as csrc/powerenv.hip computes it, with float64 for every float64 of the kernels: the three-level
+    hand-over (64 samples per chunk from zero state, 64 chunks per tile scanned with P[0 ... 5], 64 tiles per step of
+    pe_carry scanned with P[6 ... 11], s' = P[12] s + z63 from step to step), forward on the grid of the extended
+    sequence, backward on the same grid from its ragged end.  `mutation`: one of MUTATIONS.  (T, lanes) float64,
+    unclamped.  For the calibration only, never a reference."""
+    assert mutation is None or mutation in MUTATIONS, mutation
+    x = np.asarray(x)
+    edge = ib.padlen(sos)
+    u = squares(x, np.float64)
+    ext = np.concatenate([2*u[0] - u[edge:0:-1], u, 2*u[-1] - u[-2:-(edge + 2):-1]])
+    E, lanes = ext.shape
+    P = transition_powers(sos)
+    if mutation is not None and mutation.startswith('P['):
+        b = int(mutation[2:mutation.index(']')])
+        P[b] = P[b - 1] if mutation.endswith('P[%d]' % (b - 1)) else 0.0
+    coef = ib._coef(sos, np.float64)
+    zi = ib.sosfilt_zi(sos, np.float64).reshape(-1)
+    slack = -E % TILE
+    zeros = np.zeros((slack, lanes))
+    yf = _emu_pass(coef, P, np.concatenate([ext, zeros]), 0, zi[:, None]*ext[0][None, :], mutation, False)[:E]
+    yb = _emu_pass(coef, P, np.concatenate([zeros, yf[::-1]]), slack, zi[:, None]*yf[-1][None, :], mutation, True)[slack:]
+    return yb[::-1][edge:edge + len(x)]

@@ -19,6 +19,11 @@ extended trace differ.  Its section also covers what only that call has: pitches
 gain other than pi/2, y == x and y over the tail of x (the header's "x and y may overlap"), non-finite samples in one
 lane, the pad length's edge and the limit of 16 plans.
 
+Warm-ups that start inside the trace (iir_bound.T_WARM: 64 and 48 tiles + 5 samples, longer than the 26- and 15-tile
+warm-ups of the 20 Hz low-pass and the 100 Hz high-pass): hipdsp_sosfilt, hipdsp_envelope and the fused launches in three
+segments, the planner's and one-tile segments, each run after asserting that its segmentation does start segments from
+zero state in mid-trace, on the far side of a loud passage.
+
 A failure names the path, the filter, the segmentation, the lane (family) and the window; test_zz_worst_per_path
 prints the worst ratio e_w / (2^-24 r_w) of every path measured (run with -s).
 """
@@ -317,6 +322,168 @@ def test_chain_split_frames(bp, env):
         note('chain_split_frames, band-pass', ib.assert_within(gf, ref, q, 'chain_split_frames, %s, %s' % (bp, seg)))
         runs.append((seg, gf[:, lanes], ge[:, lanes]))
     judge_envelopes('chain_split_frames, envelope', esos, runs, 0, 'chain_split_frames, %s + %s' % (bp, env), between=True)
+
+
+# ---- warm-ups that start inside the trace -----------------------------------------------------------------------------
+# At T_LONG every warm-up of the slow filters is clipped at the start of the trace.  Here a segment starts from zero state
+# in mid-trace, and a condition on the segmentation that actually runs keeps it so: a test whose planner one day picks a
+# single segment fails instead of passing without testing.
+
+WARM_SEGMENTATIONS = SEGMENTATIONS[1:]                   # (one segment has no warm-up)
+# forward segments of two to five tiles are where env_fix_kernel once multiplied (A^TILE)^segment out in float64 and lost
+# the states behind a loud passage (3e-7, 25 to 35 roundings of the envelope on `stepdown`); of 65 tiles these are 2, 3, 4, 5
+SHORT_SEGMENTATIONS = tuple(('at most %d segments' % n, (('max_segments', n),)) for n in (33, 22, 17, 13))
+FORWARD_ALONE, FORWARD_FUSED, BACKWARD = -1, -2, 4       # the planner's cost tables (csrc/sos_plan.hip: tile_step_cost)
+
+
+def planned(opts, model, n_tiles, channels, warm, w_cap=16):
+    """Segment length in tiles of a single-wave sweep under the context options `opts` (csrc/sos_device.h:
+    plan_segments), through hipdsp_sos_segments_host."""
+    import ctypes
+    from audian_amd import _lib
+    o = dict(DEFAULTS)
+    o.update(dict(opts))
+    w_max = min(o['sos_waves_per_cu'] or 16, w_cap)
+    length, count = ctypes.c_int64(), ctypes.c_int()
+    _lib.check(_lib.lib.hipdsp_sos_segments_host(o['n_cus'], w_max, 0 if o['sos_waves_min'] >= w_max else model, o['max_segments'],
+                                                 n_tiles*ib.TILE, channels, warm, ctypes.byref(length), ctypes.byref(count)))
+    assert length.value % ib.TILE == 0 and count.value == -(-n_tiles//(length.value//ib.TILE))
+    return int(length.value)//ib.TILE
+
+
+def forward_condition(seg_tiles, T, warm, what, need=2):
+    """At least `need` segments start from zero state at least one tile inside the trace, one of them behind the loud
+    quarter of `stepdown`."""
+    assert warm % ib.TILE == 0
+    cut = ib.cut_warmups(-(-T//ib.TILE), seg_tiles, warm//ib.TILE)
+    assert len(cut) >= need, '%s: %d-tile segments, warm-up %d tiles: %d warm-ups start inside the trace' % (
+        what, seg_tiles, warm//ib.TILE, len(cut))
+    assert any(t*ib.TILE >= T//4 for t, _ in cut), what + ': no such segment behind the loud quarter of stepdown'
+
+
+def backward_condition(seg_tiles, n_tiles, T, warm, what, need=2):
+    """The same for a backward sweep, whose tiles count from the end of the extended trace: a segment that starts at
+    reversed tile t runs downwards from sample (n_tiles - t) 2048, its warm-up from (n_tiles - t + warm) 2048; one of
+    them starts in front of the loud half of `stepup`."""
+    assert warm % ib.TILE == 0
+    cut = ib.cut_warmups(n_tiles, seg_tiles, warm//ib.TILE)
+    assert len(cut) >= need, '%s: %d-tile segments, warm-up %d tiles: %d warm-ups start inside the trace' % (
+        what, seg_tiles, warm//ib.TILE, len(cut))
+    assert any((n_tiles - t)*ib.TILE <= T//2 for t, _ in cut), what + ': no such segment in front of the loud half of stepup'
+
+
+def backward_need(seg):
+    """Three segments of the 65 tiles are 22 tiles each: only the third one (from reversed tile 44, its warm-up from
+    tile 18) fits a 26-tile warm-up in front of it.  Every other segmentation has at least two."""
+    return 1 if seg == 'three segments' else 2
+
+
+def warm_opts(opts, more=()):
+    return (('n_cus', 256),) + opts + more
+
+
+def test_warmup_sosfilt():
+    """hipdsp_sosfilt, hp3 100 Hz @ 192 kHz (warm-up 15 tiles) over 48 tiles + 5: in three segments of 17 tiles the second
+    and the third start from zero state at tiles 2 and 19."""
+    from audian_amd import hipdsp
+    case = ib.WARM_BANDPASS
+    sos, rate, _ = bandpass(case)
+    fams = ib.WARM_FAMILIES
+    T, C = ib.T_WARM[case], len(fams)
+    x = ib.families(fams, T, rate)
+    ref, q = ib.sosfilt_case(sos, x)
+    capped(q, case)
+    ib.assert_in_range(ref, case)
+    c = gh.ctx()
+    dx, plan = gh.to_planar(c, x), hipdsp.SosPlan(c, sos)
+    warm = plan.info()[0]
+    assert warm == ib.WARM_TILES[case]*ib.TILE
+    for seg, opts in WARM_SEGMENTATIONS:
+        what = 'hipdsp_sosfilt, %s, %d frames, %s' % (case, T, seg)
+        forward_condition(planned(warm_opts(opts), FORWARD_ALONE, -(-T//ib.TILE), C, warm), T, warm, what)
+        with options(c, warm_opts(opts)):
+            dy = fresh(c, C, T)
+            hipdsp.sosfilt(c, plan, dx, T, dy, T, C, T, 0)
+            got = dy.to_host().T
+        note('hipdsp_sosfilt, warm-ups inside the trace', ib.assert_within(got, ref, q, what))
+
+
+def test_warmup_envelope():
+    """hipdsp_envelope, lp2 20 Hz @ 96 kHz (warm-up 26 tiles) over 64 tiles + 5, with and without the register prefetch:
+    the backward sweep's segments start from zero state with the future cut off, and the forward sweep hands its states
+    over sums of up to 27 segments (env_fix_kernel); once more in segments of 2, 3, 4 and 5 tiles."""
+    from audian_amd import hipdsp
+    case = ib.WARM_ENVELOPE
+    sos, rate, _ = ib.design(case, ib.ENVELOPES)
+    fams = ib.WARM_FAMILIES
+    T, C = ib.T_WARM[case], len(fams)
+    x = ib.families(fams, T, rate)
+    ref, q = ib.envelope_case(sos, x)
+    capped(q, case)
+    ib.assert_in_range(ref, case)
+    c = gh.ctx()
+    dx, plan = gh.to_planar(c, x), hipdsp.SosPlan(c, sos)
+    warm, edge = plan.info()
+    assert warm == ib.WARM_TILES[case]*ib.TILE and edge == ib.padlen(sos)
+    n_tiles = -(-(T + edge)//ib.TILE)
+    assert [planned(warm_opts(opts), FORWARD_FUSED, n_tiles, C, 0) for _, opts in SHORT_SEGMENTATIONS] == [2, 3, 4, 5]
+    for seg, opts in WARM_SEGMENTATIONS + SHORT_SEGMENTATIONS:
+        for prefetch in (1, 0) if (seg, opts) in WARM_SEGMENTATIONS else (1,):
+            what = 'hipdsp_envelope, %s, %d frames, %s, sos_prefetch %d' % (case, T, seg, prefetch)
+            backward_condition(planned(warm_opts(opts), BACKWARD, n_tiles, C, warm, 8), n_tiles, T, warm, what, backward_need(seg))
+            with options(c, warm_opts(opts, (('sos_prefetch', prefetch),))):
+                got = run_envelope(c, plan, dx, T, C)
+            note('hipdsp_envelope, warm-ups inside the trace', ib.assert_within(got, ref, q, what))
+
+
+@pytest.mark.parametrize('shifted', [False, True], ids=['from sample 0', 'shifted grid'])
+def test_warmup_fused(shifted):
+    """bp2 300-3000 Hz in front of the 20 Hz envelope over 64 tiles + 5 through hipdsp_sosfilt_envelope (phase 0, phases 1
+    + 2) and hipdsp_chain_forward 2048/1024 + phase 2: the band-pass's short warm-ups and the envelope's exact hand-over
+    forward, the envelope's 26-tile warm-ups backward.  Once more on the shifted grid (spec_first 777, env_first
+    ENV_FIRST[1]) in one-tile segments.  Every envelope against the reference of its own launch's float32 band-pass
+    output, all of them lanes of one reference run."""
+    from audian_amd import hipdsp
+    bp, env = ib.WARM_FUSED, ib.WARM_ENVELOPE
+    nfft, hop = 2048, 1024
+    sos, rate, _ = bandpass(bp)
+    esos = ib.design(env, ib.ENVELOPES)[0]
+    fams = ib.WARM_FAMILIES
+    T, C = ib.T_WARM[env], len(fams)
+    x = ib.families(fams, T, rate)
+    ref, q = ib.sosfilt_case(sos, x)
+    capped(q, bp)
+    c = gh.ctx()
+    dx, fplan, eplan = gh.to_planar(c, x), hipdsp.SosPlan(c, sos), hipdsp.SosPlan(c, esos)
+    warm_f, (warm_e, edge) = fplan.info()[0], eplan.info()
+    assert warm_e == ib.WARM_TILES[env]*ib.TILE
+    spec_first, env_first = (777, ib.ENV_FIRST[1]) if shifted else (0, 0)
+    n_tiles = -(-(T + edge)//ib.TILE) if not shifted else (T - env_first + edge)//ib.TILE     # (shifted: a lower bound)
+    runs = []
+    for seg, opts in WARM_SEGMENTATIONS[2:] if shifted else WARM_SEGMENTATIONS:
+        o = warm_opts(opts)
+        what = '%s + %s, %d frames, %s%s' % (bp, env, T, seg, ', shifted grid' if shifted else '')
+        forward_condition(planned(o, FORWARD_FUSED, -(-T//ib.TILE), C, warm_f), T, warm_f, 'hipdsp_sosfilt_envelope, ' + what)
+        backward_condition(planned(o, BACKWARD, n_tiles, C, warm_e, 8), n_tiles, T - env_first, warm_e, what, backward_need(seg))
+        for phases in ((0,), (1, 2)):
+            with options(c, o):
+                yf, ye = fresh(c, C, T), fresh(c, C, T - env_first)
+                for phase in phases:
+                    hipdsp.sosfilt_envelope(c, fplan, eplan, dx, T, yf, T, ye, T - env_first, C, T, clamp=False, phase=phase,
+                                            env_first=env_first)
+                gf, ge = yf.to_host().T, ye.to_host().T
+            label = 'hipdsp_sosfilt_envelope, %s, phase %s' % (seg, '+'.join(str(p) for p in phases))
+            note('hipdsp_sosfilt_envelope, warm-ups inside the trace, band-pass', ib.assert_within(gf, ref, q, label + ', ' + what))
+            runs.append((label, gf, ge))
+        with options(c, o):
+            seg_frames, n_seg = hipdsp.chain_plan(c, fplan, eplan, C, T)
+            assert seg_frames % ib.TILE == 0 and n_seg >= 2
+            forward_condition(seg_frames//ib.TILE, T, warm_f, 'hipdsp_chain_forward, ' + what)
+            gf, ge = run_chain(c, fplan, eplan, dx, T, C, nfft, hop, rate, spec_first, env_first)
+        label = 'hipdsp_chain_forward %d/%d + phase 2, %s' % (nfft, hop, seg)
+        note('hipdsp_chain_forward 2048/1024, warm-ups inside the trace, band-pass', ib.assert_within(gf, ref, q, label + ', ' + what))
+        runs.append((label, gf, ge))
+    judge_envelopes('fused launches, warm-ups inside the trace, envelope', esos, runs, env_first, '%s + %s, %d frames' % (bp, env, T))
 
 
 # ---- hipdsp_envelope_multi ---------------------------------------------------------------------------------------

@@ -32,7 +32,7 @@ def note(key, value):
 @functools.lru_cache(maxsize=None)
 def plan_for(name):
     from audian_amd import hipdsp
-    return hipdsp.SosPlan(gh.ctx(), pd.design(name)[0])
+    return hipdsp.SosPlan(gh.ctx(), (pd.design if name in pd.FILTERS else pd.long_design)(name)[0])
 
 
 def run(plan, x, first=0, step=1, n_out=None, gain=1.0, root=False, c=None, x_slack=3, y_slack=5, x_base=1, y_base=3,
@@ -100,6 +100,42 @@ def test_every_window_within_the_bound(name):
     note('worst window ratio, ' + name, judge(got, ref, q, name))
     negative = ref < -(1.0 + ib.MARGIN*np.max(q))*ib.ULP*np.max(np.abs(ref))
     assert np.all(got[negative] == 0)
+
+
+# ---- rows longer than the filter's memory -------------------------------------------------------------------------------
+
+@pytest.mark.parametrize('name,frames', [(name, frames) for name in pd.LONG_FILTERS for frames in pd.long_rows(name)])
+def test_long_rows_within_the_bound(name, frames):
+    """Rows whose tiles' entering states come through every power of pe_carry's ladder: 6, 10 and 18 tiles of a two-section
+    plan (P[8], P[9], P[10]; E one before, on and one behind a multiple of 4096) and 131 tiles of a one-section plan (P[6] ...
+    P[12], three steps of pe_carry's loop, the last one ragged), which tests/test_power_envelope_host.py shows to catch each
+    of them.  Every window under the same bound.  The device takes milliseconds; the 131-tile case takes 15 s on the CPU for
+    its longdouble reference and float64 run (shared with the grid test below), the others 1 to 5 s."""
+    sos, rate, fams = pd.long_design(name)
+    x = ib.families(list(fams), frames, rate)
+    ref, q = pd.case(sos, x)
+    what = '%s, %d frames' % (name, frames)
+    ib.assert_in_range(ref, what)
+    assert np.all(q <= ib.Q_CAP)
+    assert frames in pd.long_rows(name) and pd.tiles_of(sos, frames) in (6, 10, 18, 131)
+    got = run(plan_for(name), x)
+    note('worst window ratio, %s, %d tiles' % (name, pd.tiles_of(sos, frames)), judge(got, ref, q, what))
+
+
+def test_long_grid_is_exact():
+    """The 131-tile row on a grid (step > 1, first > 0, root = 1): the full-rate result picked on the grid, byte for byte,
+    and that full-rate result is the root of the power that test_long_rows_within_the_bound judges."""
+    sos, rate, fams = pd.long_design(pd.LONG)
+    x = ib.families(list(fams), pd.T_ROW, rate)
+    plan = plan_for(pd.LONG)
+    full = run(plan, x, gain=1.0, root=True)
+    assert full.shape == x.shape
+    assert full.tobytes() == np.sqrt(run(plan, x)).tobytes()
+    for step, first in ((19, 7), (4097, 4099)):
+        n_max = pd.grid_size(pd.T_ROW, first, step)
+        for n_out in (n_max, n_max - 1):
+            got = run(plan, x, first, step, n_out, gain=1.0, root=True)
+            assert got.tobytes() == np.ascontiguousarray(full[first::step][:n_out]).tobytes(), (step, first, n_out)
 
 
 # ---- lengths ----------------------------------------------------------------------------------------------------------

@@ -13,6 +13,9 @@
 4. Two wrong versions violate the bound: the cascade's state rounded to float32 at every tile border -- while still
    passing rel_err < 1e-4 on the same data, the gap this bound closes -- and eight-tile segments warmed up over one
    tile only, on the filter with the longest memory.
+   Rows long enough for a warm-up to start in mid-trace (iir_bound.T_WARM): the model cut into three segments passes
+   with the plan's own warm-up and misses the bound with half of it, forward (the past cut off, `stepdown`) and in the
+   envelope's backward pass (the future cut off, `stepup`); the shortest warm-up that still passes is recorded.
 5. hipdsp_envelope_multi (a cascade over several plans, float32 between them): every case of iir_bound.MULTI meets the
    cap and the range at T_MULTI; the restatement of a five- and an eight-section cascade is the oracle's; the model of
    the call with its 2P - 1 roundings lies inside the bound with iir_bound.handover_term (1 for 16); five wrong
@@ -194,6 +197,102 @@ def test_a_one_tile_warm_up_is_caught():
     assert np.any(rho > 1.0 + ib.MARGIN*q)
     with pytest.raises(AssertionError):
         ib.assert_within(wrong, ref, q, case)
+
+
+# ---- warm-ups that start inside the trace -----------------------------------------------------------------------------
+
+def plan_warm_tiles(sos):
+    """The warm-up of a plan in tiles (hipdsp_sos_plan_host, no GPU)."""
+    import ctypes
+    from audian_amd import _lib
+    sos = np.ascontiguousarray(sos, dtype=np.float64)
+    warm = ctypes.c_int64()
+    _lib.check(_lib.lib.hipdsp_sos_plan_host(ctypes.c_void_p(sos.ctypes.data), len(sos), ctypes.byref(warm), None, None))
+    assert warm.value % ib.TILE == 0
+    return int(warm.value)//ib.TILE
+
+
+# the shortest warm-up (tiles) with which the three-segment model still meets the bound on the four families at their
+# levels, of the plan's 15 / 26 / 26; steps of 120 dB in place of 80 (q within the cap) move it to 9 / 16 / 16 tiles and
+# no further: no admissible level makes three quarters of a warm-up (11 / 19 tiles) fail
+SHORTEST = {(ib.WARM_BANDPASS, 'forward'): 8, (ib.WARM_ENVELOPE, 'forward'): 16, (ib.WARM_ENVELOPE, 'backward'): 14}
+
+
+def check_warmups(model, ref, q, what, warm, shortest, lane):
+    """The plan's own warm-up and the shortest recorded one pass, one tile less and half the plan's fail, the latter on
+    `lane`, the family that has quiet windows on the far side of a loud passage."""
+    assert shortest <= 3*warm//4 and warm//2 < shortest
+    for w in (warm, shortest):
+        worst = ib.assert_within(model(w).astype(np.float32), ref, q, '%s, warm-up %d tiles' % (what, w))
+        print('%s: warm-up %d tiles, worst %.3f' % (what, w, worst))
+    for w in sorted({shortest - 1, warm//2}, reverse=True):
+        got = model(w).astype(np.float32)
+        share = ib.allowance_share(got, ref, q)
+        print('%s: warm-up %d tiles misses by %s' % (what, w, ' '.join('%.3g' % v for v in share)))
+        with pytest.raises(AssertionError):
+            ib.assert_within(got, ref, q, '%s, warm-up %d tiles' % (what, w))
+        if w == warm//2:
+            assert share[lane] > 1.0, (what, w, share)
+
+
+def test_warmup_inside_the_trace_forward():
+    """hp3 100 Hz @ 192 kHz at 48 tiles + 5 (the longdouble reference takes 3.8 s here): three segments of 17 tiles, the
+    second and third start from zero state in mid-trace.  Warm-ups of 15 (the plan's) and 8 tiles pass, 7 tiles miss
+    the bound (1.2), as does half the plan's warm-up."""
+    case = ib.WARM_BANDPASS
+    sos, rate, _ = ib.design(case)
+    warm = plan_warm_tiles(sos)
+    assert warm == ib.WARM_TILES[case] == 15
+    T = ib.T_WARM[case]
+    assert len(ib.cut_warmups(-(-T//ib.TILE), 17, warm)) == 2
+    x = ib.families(ib.WARM_FAMILIES, T, rate)
+    ref, run = ib.sosfilt_runs(sos, x)
+    q = check_case(ref, run, '%s, T %d' % (case, T))
+    check_warmups(lambda w: ib.segmented_sosfilt(sos, x, w), ref, q, case, warm, SHORTEST[case, 'forward'],
+                  ib.WARM_FAMILIES.index('stepdown'))
+
+
+def test_warmup_inside_the_trace_envelope():
+    """lp2 20 Hz @ 96 kHz at 64 tiles + 5 (the longdouble references take 2.1 s for the forward pass and 4.3 s for the
+    envelope here): three segments of 22 tiles, the third starts at tile 44 from zero state at tile 18.  As a forward
+    sweep (a band-pass with this memory; `stepdown` shows the past that is cut off) warm-ups of 26 and 16 tiles pass,
+    15 (1.7) and 13 (11) miss the bound.  As the envelope's backward pass (`stepup` shows the future that is cut off) 26
+    and 14 tiles pass, 13 tiles miss it (2.4)."""
+    case = ib.WARM_ENVELOPE
+    sos, rate, _ = ib.design(case, ib.ENVELOPES)
+    warm = plan_warm_tiles(sos)
+    assert warm == ib.WARM_TILES[case] == 26
+    T = ib.T_WARM[case]
+    assert ib.cut_warmups(-(-T//ib.TILE), 22, warm) == [(44, 18)]
+    assert ib.cut_warmups(-(-(T + ib.padlen(sos))//ib.TILE), 22, warm) == [(44, 18)]
+    x = ib.families(ib.WARM_FAMILIES, T, rate)
+    ref, run = ib.sosfilt_runs(sos, x)
+    q = check_case(ref, run, '%s, T %d, forward' % (case, T))
+    check_warmups(lambda w: ib.segmented_sosfilt(sos, x, w), ref, q, case + ', forward', warm, SHORTEST[case, 'forward'],
+                  ib.WARM_FAMILIES.index('stepdown'))
+    ref, run = ib.envelope_runs(sos, x)
+    q = check_case(ref, run, '%s, T %d, envelope' % (case, T))
+    check_warmups(lambda w: ib.segmented_envelope(sos, x, w), ref, q, case + ', backward', warm, SHORTEST[case, 'backward'],
+                  ib.WARM_FAMILIES.index('stepup'))
+
+
+def test_warmup_fused_pair_meets_the_cap():
+    """The fused launches' long case: the 20 Hz envelope of the 300-3000 Hz band-pass output (the float64 run rounded to
+    float32 stands in for the launch's own), from sample 0 and from ENV_FIRST[1]: the cap, the range, and the model with
+    the sweeps' float32 extensions inside the bound with 1 for 16."""
+    sos, rate, _ = ib.design(ib.WARM_FUSED)
+    esos = ib.design(ib.WARM_ENVELOPE, ib.ENVELOPES)[0]
+    assert plan_warm_tiles(sos) <= 2
+    x = ib.families(ib.WARM_FAMILIES, ib.T_WARM[ib.WARM_ENVELOPE], rate)
+    ref, run = ib.sosfilt_runs(sos, x)
+    check_case(ref, run, ib.WARM_FUSED + ', T %d' % len(x))
+    yf = run.astype(np.float32)
+    for first in ib.ENV_FIRST:
+        what = '%s + %s from %d, T %d' % (ib.WARM_FUSED, ib.WARM_ENVELOPE, first, len(x))
+        ref, run = ib.envelope_runs(esos, yf[first:])
+        q = check_case(ref, run, what)
+        model = ib.sosfiltfilt(esos, yf[first:], np.float64, clamp=False, right_ext_f32=True, left_ext_f32=first > 0)
+        ib.assert_within(model.astype(np.float32), ref, q, what + ', float32 extensions', margin=1.0)
 
 
 # ---- hipdsp_envelope_multi ---------------------------------------------------------------------------------------------

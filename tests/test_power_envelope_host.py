@@ -1,6 +1,7 @@
 """The power envelope without a GPU: the definition (power_envelope_definition.py) against what the reference's own
 functions recorded (tests/golden/power_envelope.npz), the calibration of the per-window bound the GPU tests apply, the
-facade's host fallback, the step rule, the absolute grid of BufferedPowerEnvelope and a host-only walk of detect_songs."""
+facade's host fallback, the step rule, the absolute grid of BufferedPowerEnvelope, a host-only walk of detect_songs and the
+calibration of the rows longer than the filter's memory (power_envelope_definition.carry_emulation and its mutations)."""
 
 from math import ceil
 
@@ -310,3 +311,70 @@ def test_bound_calibration(name):
         assert np.any((share > 1.0) & (rel < 1e-5)), (name, which, share, rel)
         if which != 'extension of the samples':             # (that one is gross where the trace's ends are loud)
             assert np.all(rel < 1e-5), (name, which, rel)
+
+
+# ---- rows longer than the filter's memory: every power of the ladder, every step of the carry --------------------------------
+
+LONG_ROWS = [(name, frames) for name in pd.LONG_FILTERS for frames in pd.long_rows(name)]
+
+
+def test_carry_emulation_is_the_sequential_run():
+    """The emulation restates the same recurrence: on the short cases it is the sequential float64 run to float64 round-off
+    (of the row's largest value: the non-normal powers of a two-section cascade reach 7e5)."""
+    for name in pd.FILTERS:
+        sos, rate, fams = pd.design(name)
+        x = ib.families(list(fams), pd.T_CASE, rate)
+        run = pd.runs(sos, x)[1]
+        emu = pd.carry_emulation(sos, x)
+        assert np.max(np.abs(emu - run)/np.max(np.abs(run), axis=0)) < 1e-12, name
+    assert pd.powers_reached(4) == list(range(8)) and pd.powers_reached(5) == list(range(8))
+    assert pd.powers_reached(6) == list(range(9)) and pd.powers_reached(18) == list(range(11))
+    assert pd.powers_reached(128) == list(range(12)) and pd.powers_reached(129) == list(range(13))
+
+
+@pytest.mark.parametrize('name,frames', LONG_ROWS)
+def test_carry_calibration(name, frames):
+    """Rows of 6, 10, 18 (two sections) and 131 tiles (one section): the case meets the cap and the range, the float64
+    emulation of csrc/powerenv.hip's three-level hand-over lies inside the bound the GPU test applies, and every mutation of
+    it that the row claims to reach misses the bound: P[b] = 0 and P[b] = P[b - 1] for every b of powers_reached(tiles), and on
+    the 131-tile row the step hand-over without its P[12] s term and the downward carry's blocks of 64 taken from the wrong
+    end of the ragged row.  A mutation the row does NOT reach leaves the emulation's bits alone, so the list of what a row
+    reaches is not wishful.  Out of reach of the two-section rows: P[11] (max |.| 3.3e-24) and P[12] (4.5e-54) of lp3 8 Hz,
+    which only the one-section 131-tile row shows (there 1.9e-4 and 3.5e-8).
+
+    Measured when written, shares of the allowance (1 + 16 q) 2^-24 r_w: emulation 0.94 / 0.88 / 0.93 / 0.996; weakest
+    mutants P[10] = 0 at 18 tiles 8.7, P[12] = 0 and the missing P[12] s at 131 tiles 8.5e3 (first in tile 88 of stepdown
+    through the backward carry, 1.1e7 on stepup), every other one above 1e5.  The 131-tile case takes 15 s here for its
+    longdouble reference and float64 run (two passes over 532497 samples each), the others 1 to 5 s."""
+    sos, rate, fams = pd.long_design(name)
+    tiles = pd.tiles_of(sos, frames)
+    E = frames + 2*ib.padlen(sos)
+    assert len(sos) == (1 if name == pd.LONG else 2)
+    if name == pd.LONG:
+        assert tiles == 131 and tiles > 2*pd.BLOCK and tiles % pd.BLOCK != 0 and E % pd.TILE != 0
+    else:
+        assert E in pd.MIDDLE_E and min(abs(E % pd.TILE - v) for v in (0, 1, pd.TILE - 1)) == 0
+    x = ib.families(list(fams), frames, rate)
+    ref, q = pd.case(sos, x)
+    what = '%s, %d frames' % (name, frames)
+    print('%s: %d tiles, q %s' % (what, tiles, ' '.join('%.2g' % v for v in q)))
+    ib.assert_in_range(ref, what)
+    assert np.all(q <= ib.Q_CAP), (what, q)
+    clean = pd.carry_emulation(sos, x)
+    worst = ib.assert_within(clean.astype(np.float32), ref, q, what + ', the emulation')
+    print('%s: the emulation %.3f' % (what, worst))
+    reached = pd.powers_reached(tiles)
+    assert max(reached) == {6: 8, 10: 9, 18: 10, 131: 12}[tiles]
+    for mutation in pd.MUTATIONS:
+        if mutation.startswith('P['):
+            claimed = int(mutation[2:mutation.index(']')]) in reached
+        else:
+            claimed = name == pd.LONG
+        got = pd.carry_emulation(sos, x, mutation)
+        if not claimed:
+            assert got.tobytes() == clean.tobytes(), (what, mutation)
+            continue
+        share = ib.allowance_share(got.astype(np.float32), ref, q)
+        print('%s, %s: misses by %s' % (what, mutation, ' '.join('%.3g' % v for v in share)))
+        with pytest.raises(AssertionError):
+            ib.assert_within(got.astype(np.float32), ref, q, what + ', ' + mutation)
