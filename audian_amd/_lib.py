@@ -125,6 +125,8 @@ _SIGNATURES = {
     'hipdsp_decibel_image_decimate': ([_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _dbl, _dbl], _int),
     'hipdsp_channel_mean': ([_vp, _vp, _i64, ctypes.POINTER(_int), _int, _i64, _i64, _dbl, _vp], _int),
     'hipdsp_stride_copy': ([_vp, _vp, _i64, _i64, _vp], _int),
+    'hipdsp_common_reference': ([_vp, _vp, _i64, _vp, _i64, _i64, _i64, ctypes.POINTER(_int), ctypes.POINTER(ctypes.c_ubyte), _int],
+                                _int),
     'hipdsp_max_nonneg': ([_vp, _vp, _i64, _vp], _int),
     'hipdsp_band_order_stats': ([_vp, _vp, _i64, _i64, _i64, _i64, _vp], _int),
     'hipdsp_unwrap': ([_vp, _vp, _i64, _i64, _i64, _dbl, _dbl, _int, _int, _vp, _i64], _int),

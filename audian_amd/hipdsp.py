@@ -476,6 +476,23 @@ def channel_mean(ctx, x, x_pitch, channels, start, n, out, heterodyne_cycles_per
                                   int(n), float(heterodyne_cycles_per_sample), _p(out)))
 
 
+CREF_MEAN, CREF_MEDIAN = 0, 1                # HIPDSP_CREF_MEAN / _MEDIAN
+CREF_TILE = 1024                             # HIPDSP_CREF_TILE: frames per workgroup up to 16 reference channels a group
+CREF_TILES = (32, 512, 1024)                 # ... and the tiles of the other kernels: means beyond 64, up to 64
+CREF_MODES = {'mean': CREF_MEAN, 'median': CREF_MEDIAN}
+
+
+def common_reference(ctx, x, x_pitch, y, y_pitch, channels, frames, group, use=None, mode='mean'):
+    """hipdsp_common_reference: y[c] = x[c] - mean or median over the reference channels of c's group.  `group`: one
+    id in [0, channels) or -1 (pass through) per channel; `use`: 0/1 per channel (None: all 1); `mode`: 'mean',
+    'median' or the C constant."""
+    _count('common_reference')
+    garr = (ctypes.c_int*len(group))(*[int(g) for g in group])
+    uarr = None if use is None else (ctypes.c_ubyte*len(use))(*[1 if u else 0 for u in use])
+    check(lib.hipdsp_common_reference(ctx.handle, _p(x), int(x_pitch), _p(y), int(y_pitch), int(channels), int(frames),
+                                      garr, uarr, int(CREF_MODES.get(mode, mode))))
+
+
 def stride_copy(ctx, x, n, step, out):
     check(lib.hipdsp_stride_copy(ctx.handle, _p(x), int(n), int(step), _p(out)))
 

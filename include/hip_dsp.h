@@ -469,6 +469,37 @@ int hipdsp_channel_mean(hipdsp_ctx *ctx, const float *x, int64_t x_pitch, const 
                         float *out);
 int hipdsp_stride_copy(hipdsp_ctx *ctx, const float *x, int64_t n, int64_t step, float *out);
 
+/* Common-reference subtraction across the channels of a planar trace (the reference's "Subtract common mean" plug-in,
+ * and the median that arrays use instead).  host_group[c] is the group of channel c, an id in [0, channels), or -1 for
+ * a channel that passes through; host_use[c] != 0 (NULL: every channel) makes c a reference channel of its group.
+ * Per group g and sample t, with members(g) = {c : group[c] == g} and refs(g) = {c in members(g) : use[c]} in
+ * ascending c:
+ *   y[c, t] = (float)((double)x[c, t] - ref_g[t])   for every member c -- one rounding, at the end;
+ *   HIPDSP_CREF_MEAN:   ref = s / n, s the float64 sum of (double)x[k, t] over refs(g), added one by one in ascending
+ *                       channel order from 0.0, n = |refs(g)| as a double (the library is built with
+ *                       -ffp-contract=off: reproducible bit for bit);
+ *   HIPDSP_CREF_MEDIAN: the refs values at t ordered by value: the middle one for odd n, ((double)a + (double)b) * 0.5
+ *                       of the two middle ones for even n.
+ * A NaN among the refs values at t makes ref NaN (as numpy's mean and median do); infinities follow IEEE arithmetic
+ * (inf - inf = NaN); -0 and +0 compare equal, the sign of a zero RESULT is not specified.  A member with use == 0 gets
+ * the reference taken off without contributing to it (a dead or clipping channel).  Channels of group -1 are copied;
+ * in place they are neither read nor written.
+ * In place (y == x with y_pitch == x_pitch) is allowed: all inputs of a sample are read before any of its outputs is
+ * written; any other overlap is refused.  A pitch of 0 means `frames`; rows need no alignment beyond 4 bytes.
+ * HIPDSP_ERR_INVALID: a group id outside [-1, channels), a group with members but no reference channel, an unknown
+ * mode, a pitch below frames, a partial overlap, NULL pointers.  HIPDSP_ERR_UNSUPPORTED: channels > 1024, a median over
+ * more than 64 reference channels in one group.
+ * The group table travels by value in the kernel arguments: one kernel launch, no context scratch, no host
+ * synchronisation, nothing uploaded -- legal inside hipdsp_graph_begin/end.  No atomics: a group's output bytes
+ * depend on that group's rows alone.  HIPDSP_CREF_TILE is the largest number of frames one workgroup covers: 1024 when
+ * no group has more than 16 reference channels, 512 up to 64, 32 beyond (means only). */
+#define HIPDSP_CREF_MEAN   0
+#define HIPDSP_CREF_MEDIAN 1
+#define HIPDSP_CREF_TILE   1024
+int hipdsp_common_reference(hipdsp_ctx *ctx, const float *x, int64_t x_pitch, float *y, int64_t y_pitch,
+                            int64_t channels, int64_t frames, const int *host_group,
+                            const unsigned char *host_use, int mode);
+
 /* Maximum of n non-negative floats (PSD values) into out[0]; with the strided gather of
  * hipdsp_memcpy2d_d2d it serves BufferedSpectrogram.estimate_noiselevels
  * (bufferedspectrogram.py:109-126: max dB = decibel(max power), P95 of the top 1/16 band). */

@@ -258,6 +258,19 @@ for b in builds:
     logs[b['name']].append(f'{"hipdsp_power_envelope, low-pass of 1 section at 500 Hz, step 19, root":78s} {ms:8.3f} ms {(12.0*S + 4.0*C*n_out)/ms/1e6:7.0f} GB/s')
     if b is builds[-1]:
         print(logs[b['name']][-1], flush=True)
+# ---- hipdsp_common_reference: the raw buffer minus the mean / the median of its 64 channels (tools/common_reference_bench.py
+# has the groups of 16, in place, and the copy and hipdsp_unwrap over the same buffers)
+for b in builds:
+    h, ctx = b['h'], b['ctx']
+    if not hasattr(h.lib, 'hipdsp_common_reference'):
+        continue
+    for mode in ('mean', 'median'):
+        ms = min(timed(b, lambda: h.common_reference(ctx, b['buf']['dx'], T, b['buf']['df'], T, C, T, [0]*C, None, mode), 5)
+                 for _ in range(rounds))
+        ctx.synchronize()
+        logs[b['name']].append(f'{"hipdsp_common_reference, " + mode + ", one group of 64 channels":78s} {ms:8.3f} ms {8.0*S/ms/1e6:7.0f} GB/s')
+        if b is builds[-1]:
+            print(logs[b['name']][-1], flush=True)
 prefix = os.environ.get('OUT_PREFIX')
 if prefix:
     for name, lines in logs.items():
