@@ -220,13 +220,7 @@ class BufferedArray(object):
 
     def _event_arguments(self, thresholds, min_gap, min_duration, start, stop):
         """(per-channel float64 thresholds, min_gap frames, min_len frames, first, last relative to the buffer)."""
-        if len(self.shape) > 2:
-            raise TypeError('detect_events is for traces, not for spectrogram-shaped data')
-        n = len(self._buf())
-        a = 0 if start is None else int(start) - self.offset
-        b = n if stop is None else int(stop) - self.offset
-        if a < 0 or b > n or b < a:
-            raise IndexError('range outside the loaded buffer')
+        a, b = self._trace_range('detect_events', start, stop)
         thr = np.asarray(thresholds, dtype=np.float64)
         if thr.ndim > 0 and thr.shape != (self.channels,):
             raise ValueError('thresholds: one value or one per channel')
@@ -293,22 +287,14 @@ class BufferedArray(object):
     def _spectra_arguments(self, regions, nfft, hop, step):
         """((R, 3) int64 table of channel, start, stop relative to the buffer, hop) of a region_spectra call."""
         from .spectra import MAX_NFFT, MIN_NFFT
-        if len(self.shape) > 2:
-            raise TypeError('region_spectra is for traces, not for spectrogram-shaped data')
+        self._require_trace('region_spectra')
         nfft = int(nfft)
         if nfft < MIN_NFFT or nfft > MAX_NFFT or nfft & (nfft - 1):
             raise ValueError('nfft %d is not a power of two in [%d, %d]' % (nfft, MIN_NFFT, MAX_NFFT))
         hop = nfft//2 if hop is None else int(hop)
         if hop < 1 or hop > nfft or int(step) < 1:
             raise ValueError('hop %d not in [1, nfft], or step %d < 1' % (hop, int(step)))
-        tab = np.asarray([(int(c), int(a), int(b)) for c, a, b in regions], dtype=np.int64).reshape(-1, 3)
-        if len(tab) and (tab[:, 0].min() < 0 or tab[:, 0].max() >= self.channels):
-            raise IndexError('channel outside the trace')
-        tab[:, 1:] -= self.offset
-        n = len(self._buf())
-        if len(tab) and (tab[:, 1].min() < 0 or tab[:, 2].max() > n or (tab[:, 2] < tab[:, 1]).any()):
-            raise IndexError('range outside the loaded buffer')
-        return tab, hop
+        return self._region_table(regions, 'region_spectra'), hop
 
     def region_spectra(self, regions, nfft, hop=None, step=1):
         """Welch power spectral densities of frames [start, stop) (absolute, inside the current buffer) of one channel
@@ -340,10 +326,9 @@ class BufferedArray(object):
         return freqs, powers.astype(np.float64)
 
     def _region_table(self, regions, what):
-        """(R, 3) int64 table of channel, start, stop relative to the buffer of a region_filtfilt / region_crossings
-        call."""
-        if len(self.shape) > 2:
-            raise TypeError('%s is for traces, not for spectrogram-shaped data' % what)
+        """(R, 3) int64 table of channel, start, stop relative to the buffer of a region_spectra / region_filtfilt /
+        region_crossings call."""
+        self._require_trace(what)
         tab = np.asarray([(int(c), int(a), int(b)) for c, a, b in regions], dtype=np.int64).reshape(-1, 3)
         if len(tab) and (tab[:, 0].min() < 0 or tab[:, 0].max() >= self.channels):
             raise IndexError('channel outside the trace')
@@ -458,10 +443,14 @@ class BufferedArray(object):
         stats = self.region_stats([(a, b)])[0]
         return stats[:, 1] + float(factor)*stats[:, 2]
 
-    def _trace_range(self, what, start, stop):
-        """Frames [start, stop) (absolute; by default the whole buffer) relative to the buffer, for a trace."""
+    def _require_trace(self, what):
+        """TypeError when `what` is asked of spectrogram-shaped data."""
         if len(self.shape) > 2:
             raise TypeError('%s is for traces, not for spectrogram-shaped data' % what)
+
+    def _trace_range(self, what, start, stop):
+        """Frames [start, stop) (absolute; by default the whole buffer) relative to the buffer, for a trace."""
+        self._require_trace(what)
         n = len(self._buf())
         a = 0 if start is None else int(start) - self.offset
         b = n if stop is None else int(stop) - self.offset

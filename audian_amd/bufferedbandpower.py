@@ -8,7 +8,7 @@ spectrogram's device mirror, and moving the band recomputes this trace only."""
 
 import numpy as np
 
-from .buffereddata import BufferedData, _covers, _subtract
+from .buffereddata import BufferedData
 from .bufferedspectrogram import band_bins, decibel
 
 
@@ -81,27 +81,20 @@ class BufferedBandPower(BufferedData):
         frames give 0 (-inf)."""
         from . import hipdsp
         n = len(dest)
-        if n != len(source) - nbefore:
-            raise ValueError(f'could not broadcast input array from shape ({len(source) - nbefore},) '
-                             f'into shape ({n},)')
+        self._check_lengths(source, dest, nbefore)
         call = self._take_call(source, dest)
         if n == 0:
             return
-        src = self.source
-        if call is not None and isinstance(src, BufferedData) and src._dev is not None and \
-           _covers(src._dev_valid, call.soffset, call.soffset + call.snframes):
-            F = src._inner()
-            spec = src._dev.view((call.soffset + nbefore)*F, (1,))
+        on_mirror = self._source_mirror(call, nbefore)
+        if on_mirror is not None:
+            spec, spitch = on_mirror
             ddst, dpitch, is_mirror = self._device_dest(dest, call)
-            hipdsp.band_power(self.ctx, spec, src._pitch(), self.channels, n, F, [(self.k0, self.k1)], self.scale,
-                              ddst, db=self.log, min_power=self.min_power, out_pitch=dpitch)
+            hipdsp.band_power(self.ctx, spec, spitch, self.channels, n, self.source._inner(), [(self.k0, self.k1)],
+                              self.scale, ddst, db=self.log, min_power=self.min_power, out_pitch=dpitch)
             self._finish_dest(dest, ddst, dpitch, is_mirror, call)
             return
         # no mirror to read (a plain host array, a host-only graph): numpy in float64
         slab = np.asarray(source[nbefore:nbefore + n], dtype=np.float64)
         power = self.scale*np.sum(slab[:, :, self.k0:self.k1], axis=2)
         dest[...] = decibel(power, 1.0, self.min_power) if self.log else power
-        if call is not None:
-            a, b = call.doffset, call.doffset + call.dnframes
-            self._dev_valid = _subtract(list(self._dev_valid), a, b)
-            self._stale = _subtract(list(self._stale), a, b)
+        self._host_wrote(call)

@@ -6,7 +6,7 @@ channel off everything below it.  ``process()`` is one ``hipdsp_common_reference
 
 import numpy as np
 
-from .buffereddata import BufferedData, _covers, _subtract
+from .buffereddata import BufferedData
 
 METHODS = ('mean', 'median')
 
@@ -108,16 +108,11 @@ class BufferedCommonReference(BufferedData):
     def process(self, source, dest, nbefore):
         """dest = source[nbefore:] minus its groups' references (common_reference_host is the definition)."""
         from . import hipdsp
-        if len(dest) != len(source) - nbefore:
-            raise ValueError(f'could not broadcast input array from shape ({len(source) - nbefore},) into shape '
-                             f'({len(dest)},)')
+        self._check_lengths(source, dest, nbefore)
         call = self._take_call(source, dest)
         if len(dest) == 0:
             return
-        src = self.source
-        on_mirror = isinstance(src, BufferedData) and src._dev is not None and call is not None and \
-            _covers(src._dev_valid, call.soffset, call.soffset + call.snframes)
-        if on_mirror or (call is not None and not isinstance(src, BufferedData)):
+        if self._source_mirror(call) is not None or (call is not None and not isinstance(self.source, BufferedData)):
             # the source's mirror, or the loader's slab uploaded as the filter does it (kept between recomputes)
             dsrc, spitch, keep = self._device_source(source, call)
             ddst, dpitch, is_mirror = self._device_dest(dest, call)
@@ -130,7 +125,4 @@ class BufferedCommonReference(BufferedData):
         # a derived source without a mirror (a host-only graph), or plain arrays: the same definition in numpy
         slab = np.asarray(source[nbefore:]).reshape(len(dest), -1)
         dest[...] = common_reference_host(slab, self.group, self.use, self.method).reshape(dest.shape)
-        if call is not None:
-            a, b = call.doffset, call.doffset + call.dnframes
-            self._dev_valid = _subtract(list(self._dev_valid), a, b)
-            self._stale = _subtract(list(self._stale), a, b)
+        self._host_wrote(call)

@@ -30,6 +30,7 @@ _TRACE = bool(os.environ.get('AUDIAN_AMD_TRACE'))
 # A trace's device mirror is what the kernels write into: the best of this many allocations by the time of a memset over
 # each (hipdsp_malloc_probed; mirrors under 64 MiB: a plain allocation).  AUDIAN_AMD_WRITE_PROBE=1 turns the search off.
 WRITE_PROBE = int(os.environ.get('AUDIAN_AMD_WRITE_PROBE', '4'))
+_KEEP = object()               # "leave this parameter as it is" where None is a value of its own (the update() methods)
 
 
 class _Call(object):
@@ -214,6 +215,8 @@ class BufferedData(BufferedArray):
     _ctx = None
     _fused_token = False       # the source's own launch has already filled this trace's whole buffer (mirror)
     _alias_pitch = None        # the mirror is a VIEW of another device array with this row pitch (_alias_mirror)
+    _plan = None               # the device plan of self.sos and the bytes it was set from (_sos_plan)
+    _plan_key = None
 
     def __init__(self, name, source_name, tbefore=0, tafter=0, panel='none', panel_type='trace',
                  color='#00ee00', lw_thin=1.1, lw_thick=2):
@@ -262,7 +265,7 @@ class BufferedData(BufferedArray):
         if not self._stale:
             return True
         inside = [[max(r0, a), min(r1, b)] for r0, r1 in self._stale if min(r1, b) > max(r0, a)]
-        if self._dev is not None and _covers(self._dev_valid, a, b):
+        if self._mirror_valid(a, b):
             self._carry = inside
             self._stale = []                      # the old host buffer is about to be dropped
             return not _covers(inside, a, b)      # all of it stale: no host copy at all
@@ -353,7 +356,7 @@ class BufferedData(BufferedArray):
             return None
         if any(not isinstance(r, (int, np.integer, slice)) for r in rest) or len(rest) > self._hostbuf.ndim - 2:
             return None
-        if b <= a or self._dev is None or not _covers(self._dev_valid, a, b):
+        if b <= a or not self._mirror_valid(a, b):
             return None
         if not any(min(r1, b) > max(r0, a) for r0, r1 in self._stale):
             return None                                   # nothing stale in there
@@ -411,7 +414,20 @@ class BufferedData(BufferedArray):
         if old_dev is not None:
             old_dev.free()
 
+    def _mirror_valid(self, a, b):
+        """Is the device mirror valid over frames [a, b) of the buffer?"""
+        return self._dev is not None and _covers(self._dev_valid, a, b)
+
     # ---- helpers for process() implementations -----------------------------------
+    @staticmethod
+    def _check_lengths(source, dest, nbefore, step=None):
+        """numpy's error when `dest` does not hold source[nbefore:] -- with `step`, one frame per `step` of them."""
+        expect = len(source) - nbefore
+        if step is not None:
+            expect = max(0, -(-expect//step))
+        if len(dest) != expect:
+            raise ValueError(f'could not broadcast input array from shape ({expect},) into shape ({len(dest)},)')
+
     def _take_call(self, source, dest):
         call, self._pending = self._pending, None
         if call is not None and (call.snframes != len(source) or call.dnframes != len(dest)):
@@ -435,15 +451,23 @@ class BufferedData(BufferedArray):
         in its own way and takes no part in fused launches)."""
         return type(self).process is cls.process and type(self).recompute is BufferedData.recompute
 
+    def _source_mirror(self, call, first=0):
+        """(the source trace's device mirror from frame `first` of this call's slab on, its pitch in elements) when the
+        source is a trace whose mirror is valid over the slab, else None."""
+        src = self.source
+        if call is None or not isinstance(src, BufferedData) or \
+           not src._mirror_valid(call.soffset, call.soffset + call.snframes):
+            return None
+        return src._dev.view((call.soffset + first)*src._inner(), (1,)), src._pitch()
+
     def _device_source(self, source, call):
         """(device pointer holder, pitch in elements) of the source slab, planar float32.
         Uses the source trace's mirror when it is valid there, else uploads `source`."""
         from . import hipdsp
         src = self.source
-        if call is not None and isinstance(src, BufferedData) and src._dev is not None and \
-           _covers(src._dev_valid, call.soffset, call.soffset + call.snframes):
-            inner = src._inner()
-            return src._dev.view(call.soffset*inner, (1,)), src._pitch(), None
+        on_mirror = self._source_mirror(call)
+        if on_mirror is not None:
+            return on_mirror + (None,)
         if call is not None and isinstance(src, BufferedData) and src._stale:
             source = src.buffer[call.soffset:call.soffset + call.snframes]     # flushes
         n = len(source)
@@ -511,6 +535,29 @@ class BufferedData(BufferedArray):
             hipdsp.unpack(self.ctx, ddst, pitch, tmp, n, self.channels)
         dest[...] = tmp.to_host().reshape(dest.shape)
 
+    def _host_wrote(self, call):
+        """process() wrote this call's slab into the host buffer: neither the mirror nor a stale mark covers it now."""
+        if call is not None:
+            a, b = call.doffset, call.doffset + call.dnframes
+            self._dev_valid = _subtract(list(self._dev_valid), a, b)
+            self._stale = _subtract(list(self._stale), a, b)
+
+    def _zero_dest(self, ddst, dpitch, n):
+        """The trace of a design that failed: `n` zeros per channel (hipdsp_envelope without a plan)."""
+        from . import hipdsp
+        hipdsp.envelope(self.ctx, None, None, 0, ddst, dpitch, self.channels, n, 0)
+
+    def _sos_plan(self):
+        """The SosPlan of self.sos: created once, set again only when the table's bytes change."""
+        from . import hipdsp
+        key = self.sos.tobytes()
+        if self._plan is None:
+            self._plan = hipdsp.SosPlan(self.ctx, self.sos)
+        elif key != self._plan_key:
+            self._plan.set(self.sos)
+        self._plan_key = key
+        return self._plan
+
     def minmax_decimate(self, start, stop, step, channel=None):
         """Min/max screen decimation of frames [start, stop) (absolute frame indices inside
         the current buffer), `step` frames per plot point: what TraceItem.update_plot computes
@@ -528,7 +575,7 @@ class BufferedData(BufferedArray):
         nseg = (b - a + step - 1)//step
         if nseg == 0:
             return np.zeros(0) if channel is not None else np.zeros((self.channels, 0))
-        if self._dev is not None and _covers(self._dev_valid, a, b):
+        if self._mirror_valid(a, b):
             out = hipdsp.DeviceArray(self.ctx, (self.channels, 2*nseg), np.float32)
             hipdsp.minmax_decimate(self.ctx, self._dev, self._pitch(), self.channels, a, b, step, out, 2*nseg)
             res = out.to_host().astype(np.float64)
@@ -555,8 +602,7 @@ class BufferedData(BufferedArray):
         rel = [(int(a) - self.offset, int(b) - self.offset) for a, b in regions]
         if any(a < 0 or b > n or b < a for a, b in rel):
             raise IndexError('range outside the loaded buffer')
-        if not (rel and self.channels > 0 and self._dev is not None and
-                all(_covers(self._dev_valid, a, b) for a, b in rel)):
+        if not (rel and self.channels > 0 and all(self._mirror_valid(a, b) for a, b in rel)):
             return BufferedArray.region_stats(self, regions, channel)
         res = np.zeros((len(rel), self.channels, 8))
         inner = self._inner()
@@ -578,7 +624,7 @@ class BufferedData(BufferedArray):
         from . import hipdsp
         from .events import Events
         thr, gap, length, a, b = self._event_arguments(thresholds, min_gap, min_duration, start, stop)
-        if not (self.channels > 0 and b > a and self._dev is not None and _covers(self._dev_valid, a, b)):
+        if not self._on_mirror(a, b):
             return BufferedArray.detect_events(self, thresholds, min_gap, min_duration, start, stop)
         pairs = hipdsp.detect_events(self.ctx, self._dev, self._pitch(), self.channels, a, b,
                                      thr if np.ndim(thresholds) > 0 else float(thr[0]), gap, length)
@@ -586,7 +632,7 @@ class BufferedData(BufferedArray):
 
     def _on_mirror(self, a, b):
         """Can a reduction over frames [a, b) of the buffer run on the device mirror?"""
-        return self.channels > 0 and b > a and self._dev is not None and _covers(self._dev_valid, a, b)
+        return self.channels > 0 and b > a and self._mirror_valid(a, b)
 
     def find_peaks(self, height=None, threshold=None, prominence=None, wlen=None, start=None, stop=None):
         """BufferedArray.find_peaks on the device mirror when it is valid over the range (hipdsp_find_peaks: one call
@@ -604,10 +650,13 @@ class BufferedData(BufferedArray):
         shift = np.array([0.0, 0.0, self.offset, self.offset])
         return Peaks([(pos + self.offset, props + shift) for pos, props in results], self.rate, self.name)
 
+    def _regions_on_mirror(self, tab):
+        """Can a call over the (channel, start, stop) rows of `tab` (relative to the buffer) run on the device mirror?"""
+        return len(tab) > 0 and self.channels > 0 and all(self._mirror_valid(a, b) for c, a, b in tab.tolist())
+
     def _spectra_on_mirror(self, tab):
-        """Can the spectra of the (channel, start, stop) rows of `tab` (relative to the buffer) run on the mirror?"""
-        return len(tab) > 0 and self.channels > 0 and self._dev is not None and \
-            all(_covers(self._dev_valid, a, b) for c, a, b in tab.tolist())
+        """The same question for region_spectra and _spectra_peaks, which ask it here (what forces them to the host)."""
+        return self._regions_on_mirror(tab)
 
     def region_spectra(self, regions, nfft, hop=None, step=1):
         """BufferedArray.region_spectra on the device mirror when it is valid over every region (hipdsp_region_spectra:
@@ -675,7 +724,7 @@ class BufferedData(BufferedArray):
         filtered regions (a device copy of the buffer's shape takes them; only they cross to the host)."""
         from . import hipdsp
         tab, sos = self._filtfilt_arguments(regions, sos, out)
-        if not self._spectra_on_mirror(tab):
+        if not self._regions_on_mirror(tab):
             return BufferedArray.region_filtfilt(self, regions, sos, clamp, out, max_scratch)
         n = len(self._hostbuf)
         groups, first = [], 0
@@ -705,7 +754,7 @@ class BufferedData(BufferedArray):
         hipdsp_region_crossings call, 64 bytes per region come back.  Nothing is read back from the mirror."""
         from . import hipdsp
         tab = self._region_table(regions, 'region_crossings')
-        if not self._spectra_on_mirror(tab):
+        if not self._regions_on_mirror(tab):
             return BufferedArray.region_crossings(self, regions, thresholds)
         res = hipdsp.region_crossings(self.ctx, self._dev, self._pitch(), self.channels, len(self._hostbuf), tab, thresholds)
         res[:, [2, 3, 5]] += np.where(res[:, [2, 3, 5]] >= 0, self.offset, 0)
@@ -773,6 +822,12 @@ class BufferedData(BufferedArray):
         self.buffer = np.zeros((0, self.channels))
         self.plot_items = [None]*self.channels
         self.update_step(step, more_shape)
+
+    def _require_trace_source(self, source):
+        """open() of a trace that is computed from a trace: ValueError for a spectrogram-shaped source."""
+        if len(getattr(source, 'shape', ())) > 2:
+            raise ValueError(f'{self.name}: the source must be a trace (one value per frame and channel), '
+                             f'{getattr(source, "name", "it")} has shape {tuple(source.shape)}')
 
     def _source_len(self):
         src = self.source

@@ -54,9 +54,8 @@ class BufferedEnvelope(BufferedData):
         (bufferedenvelope.py:34-41).  Raises ValueError like scipy when the slab is not
         longer than the pad length."""
         from . import hipdsp
-        if self.sos is not None and len(dest) != len(source) - nbefore:
-            raise ValueError(f'could not broadcast input array from shape '
-                             f'({len(source) - nbefore},) into shape ({len(dest)},)')
+        if self.sos is not None:
+            self._check_lengths(source, dest, nbefore)
         call = self._take_call(source, dest)
         if len(dest) == 0:
             return
@@ -65,8 +64,7 @@ class BufferedEnvelope(BufferedData):
         ddst, dpitch, is_mirror = self._device_dest(dest, call)
         keep = None
         if self.sos is None:
-            hipdsp.envelope(self.ctx, None, None, 0, ddst, dpitch, self.channels,
-                            len(dest), 0)
+            self._zero_dest(ddst, dpitch, len(dest))
         else:
             dsrc, spitch, keep = self._device_source(source, call)
             if self._plans:

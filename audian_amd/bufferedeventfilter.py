@@ -8,7 +8,7 @@ filter."""
 
 import numpy as np
 
-from .buffereddata import BufferedData, _covers, _subtract
+from .buffereddata import BufferedData
 
 
 class BufferedEventFilter(BufferedData):
@@ -31,9 +31,7 @@ class BufferedEventFilter(BufferedData):
         self.skipped = []
 
     def open(self, source):
-        if len(getattr(source, 'shape', ())) > 2:
-            raise ValueError(f'{self.name}: the source must be a trace (one value per frame and channel), '
-                             f'{getattr(source, "name", "it")} has shape {tuple(source.shape)}')
+        self._require_trace_source(source)
         BufferedData.open(self, source, 1)
 
     def set_events(self, events, freqs, min_duration, factor=4.0, order=1, clamp=False):
@@ -81,22 +79,17 @@ class BufferedEventFilter(BufferedData):
         """dest[i, c] = source[nbefore + i, c]."""
         from . import hipdsp
         n = len(dest)
-        if n != len(source) - nbefore:
-            raise ValueError(f'could not broadcast input array from shape ({len(source) - nbefore},) into shape ({n},)')
+        self._check_lengths(source, dest, nbefore)
         call = self._take_call(source, dest)
         if n == 0:
             return
-        src = self.source
-        if call is not None and isinstance(src, BufferedData) and src._dev is not None and \
-           _covers(src._dev_valid, call.soffset, call.soffset + call.snframes):
+        on_mirror = self._source_mirror(call, nbefore)
+        if on_mirror is not None:
+            x, spitch = on_mirror
             ddst, dpitch, is_mirror = self._device_dest(dest, call)
-            hipdsp.memcpy2d(self.ctx, ddst, 4*dpitch, src._dev.view(call.soffset + nbefore, (1,)), 4*src._pitch(), 4*n,
-                            self.channels)
+            hipdsp.memcpy2d(self.ctx, ddst, 4*dpitch, x, 4*spitch, 4*n, self.channels)
             self._finish_dest(dest, ddst, dpitch, is_mirror, call)
             return
         # no mirror to read (a plain host array, a host-only graph)
         dest[...] = np.asarray(source[nbefore:nbefore + n], dtype=np.float64)
-        if call is not None:
-            a, b = call.doffset, call.doffset + call.dnframes
-            self._dev_valid = _subtract(list(self._dev_valid), a, b)
-            self._stale = _subtract(list(self._stale), a, b)
+        self._host_wrote(call)

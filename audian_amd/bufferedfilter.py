@@ -91,9 +91,7 @@ class BufferedFilter(BufferedData):
         """dest = sosfilt(sos, source, axis=0)[nbefore:] per channel, zero initial state;
         pass-through copy when no filter is set (bufferedfilter.py:31-36)."""
         from . import hipdsp
-        if len(dest) != len(source) - nbefore:
-            raise ValueError(f'could not broadcast input array from shape '
-                             f'({len(source) - nbefore},) into shape ({len(dest)},)')
+        self._check_lengths(source, dest, nbefore)
         call = self._take_call(source, dest)
         ns = len(source)
         if len(dest) == 0:

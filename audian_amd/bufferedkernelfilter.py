@@ -9,10 +9,9 @@ from math import ceil
 
 import numpy as np
 
-from .buffereddata import BufferedData, _covers, _subtract
+from .buffereddata import BufferedData, _KEEP
 
 MAX_KERNELS = 16
-_KEEP = object()
 
 
 def fir_same(slab, taps, first=0, step=1, n=None):
@@ -68,9 +67,7 @@ class BufferedKernelFilter(BufferedData):
         return taps
 
     def open(self, source):
-        if len(getattr(source, 'shape', ())) > 2:
-            raise ValueError(f'{self.name}: the source must be a trace (one value per frame and channel), '
-                             f'{getattr(source, "name", "it")} has shape {tuple(source.shape)}')
+        self._require_trace_source(source)
         BufferedData.open(self, source, self.step)
         self._set_range()
 
@@ -116,28 +113,22 @@ class BufferedKernelFilter(BufferedData):
         """dest[i, c] = y[c, nbefore + i*step], y the kernel over the slab `source` zero-extended at both ends."""
         from . import hipdsp
         n = len(dest)
-        expect = max(0, -(-(len(source) - nbefore)//self.step))
-        if n != expect:
-            raise ValueError(f'could not broadcast input array from shape ({expect},) into shape ({n},)')
+        self._check_lengths(source, dest, nbefore, self.step)
         call = self._take_call(source, dest)
         if n == 0:
             return
-        src = self.source
-        if call is not None and isinstance(src, BufferedData) and src._dev is not None and \
-           _covers(src._dev_valid, call.soffset, call.soffset + call.snframes):
-            x = src._dev.view(call.soffset, (1,))
+        on_mirror = self._source_mirror(call)
+        if on_mirror is not None:
+            x, spitch = on_mirror
             ddst, dpitch, is_mirror = self._device_dest(dest, call)
-            hipdsp.fir_bank(self.ctx, self._device_plan(hipdsp), x, src._pitch(), self.channels, call.snframes, nbefore,
+            hipdsp.fir_bank(self.ctx, self._device_plan(hipdsp), x, spitch, self.channels, call.snframes, nbefore,
                             self.step, n, ddst, rectify=self.threshold is not None, out_pitch=dpitch)
             self._finish_dest(dest, ddst, dpitch, is_mirror, call)
             return
         # no mirror to read (a plain host array, a host-only graph): numpy in float64
         y = fir_same(np.asarray(source[:], dtype=np.float64), self.kernel, nbefore, self.step, n)
         dest[...] = np.maximum(y - self.threshold, 0.0) if self.threshold is not None else y
-        if call is not None:
-            a, b = call.doffset, call.doffset + call.dnframes
-            self._dev_valid = _subtract(list(self._dev_valid), a, b)
-            self._stale = _subtract(list(self._stale), a, b)
+        self._host_wrote(call)
 
 
 def kernel_bank(trace, kernels, step=1, thresholds=None):
@@ -157,7 +148,7 @@ def kernel_bank(trace, kernels, step=1, thresholds=None):
     out = hipdsp.DeviceArray(ctx, (len(kernels), channels, n), np.float32)
     if n == 0 or channels == 0:
         return out
-    if isinstance(trace, BufferedData) and trace._dev is not None and _covers(trace._dev_valid, 0, frames):
+    if isinstance(trace, BufferedData) and trace._mirror_valid(0, frames):
         x, pitch = trace._dev, trace._pitch()
     else:
         host = np.asarray(trace.buffer[:], dtype=np.float32).reshape(frames, channels)

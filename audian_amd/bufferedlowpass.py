@@ -5,7 +5,7 @@ the slow envelope the detector's thresholds and events run on (songdetector.py:7
 
 import numpy as np
 
-from .buffereddata import BufferedData, _covers, _subtract
+from .buffereddata import BufferedData
 from .design import butter_sos
 
 
@@ -17,8 +17,6 @@ class BufferedLowpass(BufferedData):
         BufferedData.__init__(self, name, source, tbefore=1, panel=panel, panel_type='trace', color=color,
                               lw_thin=lw_thin, lw_thick=lw_thick)
         self.cutoff, self.filter_order, self.sos = cutoff, filter_order, None
-        self._plan = None
-        self._plan_key = None
         self._design_key = None
 
     def open(self, source):
@@ -44,35 +42,24 @@ class BufferedLowpass(BufferedData):
                 self.sos = None
             self._design_key = key
 
-    def _device_plan(self, hipdsp):
-        key = self.sos.tobytes()
-        if self._plan is None:
-            self._plan = hipdsp.SosPlan(self.ctx, self.sos)
-        elif key != self._plan_key:
-            self._plan.set(self.sos)
-        self._plan_key = key
-        return self._plan
-
     def process(self, source, dest, nbefore):
         """dest = sosfiltfilt(sos, source, axis=0)[nbefore:]; zeros when the design failed.  Raises ValueError like scipy
         when the slab is not longer than the pad length."""
         from . import hipdsp
         self._design()
-        if len(dest) != len(source) - nbefore:
-            raise ValueError(f'could not broadcast input array from shape ({len(source) - nbefore},) into shape '
-                             f'({len(dest)},)')
+        self._check_lengths(source, dest, nbefore)
         call = self._take_call(source, dest)
         if len(dest) == 0:
             return
-        src = self.source
-        if call is not None and isinstance(src, BufferedData) and src._dev is not None and \
-           _covers(src._dev_valid, call.soffset, call.soffset + call.snframes):
+        on_mirror = self._source_mirror(call)
+        if on_mirror is not None:
+            x, spitch = on_mirror
             ddst, dpitch, is_mirror = self._device_dest(dest, call)
             if self.sos is None:
-                hipdsp.envelope(self.ctx, None, None, 0, ddst, dpitch, self.channels, len(dest), 0)
+                self._zero_dest(ddst, dpitch, len(dest))
             else:
-                hipdsp.envelope(self.ctx, self._device_plan(hipdsp), src._dev.view(call.soffset, (1,)), src._pitch(), ddst,
-                                dpitch, self.channels, len(source), nbefore, rectify=False, gain=1.0, clamp=False)
+                hipdsp.envelope(self.ctx, self._sos_plan(), x, spitch, ddst, dpitch, self.channels, len(source), nbefore,
+                                rectify=False, gain=1.0, clamp=False)
             self._finish_dest(dest, ddst, dpitch, is_mirror, call)
             return
         # no mirror to read (a plain host array, a host-only graph): numpy in float64
@@ -83,7 +70,4 @@ class BufferedLowpass(BufferedData):
             slab = np.asarray(source[:]).reshape(len(source), -1)
             for c in range(slab.shape[1]):
                 dest[:, c] = host_region_filtfilt(slab[:, c], self.sos)[nbefore:]
-        if call is not None:
-            a, b = call.doffset, call.doffset + call.dnframes
-            self._dev_valid = _subtract(list(self._dev_valid), a, b)
-            self._stale = _subtract(list(self._stale), a, b)
+        self._host_wrote(call)

@@ -9,10 +9,8 @@ from math import ceil, floor
 
 import numpy as np
 
-from .buffereddata import BufferedData, _covers, _subtract
+from .buffereddata import BufferedData, _KEEP
 from .design import butter_sos
-
-_KEEP = object()
 
 
 def power_envelope_step(rate, cutoff):
@@ -86,8 +84,6 @@ class BufferedPowerEnvelope(BufferedData):
         self.fixed_step = None if step is None else max(1, int(step))
         self.root = bool(root)
         self.step, self.sos = 1, None
-        self._plan = None
-        self._plan_key = None
 
     @property
     def gain(self):
@@ -98,9 +94,7 @@ class BufferedPowerEnvelope(BufferedData):
         return self.fixed_step if self.fixed_step is not None else power_envelope_step(source.rate, self.envelope_cutoff)
 
     def open(self, source):
-        if len(getattr(source, 'shape', ())) > 2:
-            raise ValueError(f'{self.name}: the source must be a trace (one value per frame and channel), '
-                             f'{getattr(source, "name", "it")} has shape {tuple(source.shape)}')
+        self._require_trace_source(source)
         self.step = self._step_for(source)
         BufferedData.open(self, source, self.step)
         self.ampl_min, self.ampl_max = 0, 2.0*float(source.ampl_max)*(1.0 if self.root else float(source.ampl_max))
@@ -126,36 +120,23 @@ class BufferedPowerEnvelope(BufferedData):
             self.sos = None
         self.recompute_all()
 
-    def _device_plan(self, hipdsp):
-        key = self.sos.tobytes()
-        if self._plan is None:
-            self._plan = hipdsp.SosPlan(self.ctx, self.sos)
-        elif key != self._plan_key:
-            self._plan.set(self.sos)
-        self._plan_key = key
-        return self._plan
-
     def process(self, source, dest, nbefore):
         """dest[i, c] = the power envelope of the slab `source` at its frame nbefore + i*step.  Raises ValueError like
         scipy when the slab is not longer than the pad length; zeros when the design failed."""
         from . import hipdsp
         n = len(dest)
-        expect = max(0, -(-(len(source) - nbefore)//self.step))
-        if n != expect:
-            raise ValueError(f'could not broadcast input array from shape ({expect},) into shape ({n},)')
+        self._check_lengths(source, dest, nbefore, self.step)
         call = self._take_call(source, dest)
         if n == 0:
             return
-        src = self.source
-        on_mirror = call is not None and isinstance(src, BufferedData) and src._dev is not None and \
-            _covers(src._dev_valid, call.soffset, call.soffset + call.snframes)
-        if on_mirror:
+        on_mirror = self._source_mirror(call)
+        if on_mirror is not None:
+            x, spitch = on_mirror
             ddst, dpitch, is_mirror = self._device_dest(dest, call)
             if self.sos is None:
-                hipdsp.envelope(self.ctx, None, None, 0, ddst, dpitch, self.channels, n, 0)
+                self._zero_dest(ddst, dpitch, n)
             else:
-                x = src._dev.view(call.soffset, (1,))
-                hipdsp.power_envelope(self.ctx, self._device_plan(hipdsp), x, src._pitch(), self.channels, call.snframes, ddst, dpitch,
+                hipdsp.power_envelope(self.ctx, self._sos_plan(), x, spitch, self.channels, call.snframes, ddst, dpitch,
                                       nbefore, self.step, n, self.gain, self.root)
             self._finish_dest(dest, ddst, dpitch, is_mirror, call)
             return
@@ -164,7 +145,4 @@ class BufferedPowerEnvelope(BufferedData):
             dest[...] = 0.0
         else:
             dest[...] = power_envelope_host(self.sos, np.asarray(source[:]), nbefore, self.step, n, self.gain, self.root)
-        if call is not None:
-            a, b = call.doffset, call.doffset + call.dnframes
-            self._dev_valid = _subtract(list(self._dev_valid), a, b)
-            self._stale = _subtract(list(self._stale), a, b)
+        self._host_wrote(call)

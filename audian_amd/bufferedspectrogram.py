@@ -133,18 +133,15 @@ class BufferedSpectrogram(BufferedData):
         call = self._take_call(source, dest)
         nd = len(dest)
         F = self.nfft//2 + 1
-        if nd > 0 and self._take_fused(call):
-            nsource = min((nd - 1)*self.hop + self.nfft, len(source))
-            if nsource >= self.nfft:
-                self.frequencies = np.arange(F)*self.source.rate/self.nfft
-        elif nd > 0:
-            dsrc, spitch, keep = self._device_source(source, call)
-            ddst, dpitch, is_mirror = self._device_dest(dest, call)
-            hipdsp.spectrogram(self.ctx, dsrc, spitch, self.channels, len(source), self.nfft,
-                               self.hop, self.source.rate, ddst, nd, out_pitch=dpitch)
-            self._finish_dest(dest, ddst, dpitch, is_mirror, call)
-            if keep is not None or not is_mirror:
-                self.ctx.synchronize()
+        if nd > 0:
+            if not self._take_fused(call):
+                dsrc, spitch, keep = self._device_source(source, call)
+                ddst, dpitch, is_mirror = self._device_dest(dest, call)
+                hipdsp.spectrogram(self.ctx, dsrc, spitch, self.channels, len(source), self.nfft,
+                                   self.hop, self.source.rate, ddst, nd, out_pitch=dpitch)
+                self._finish_dest(dest, ddst, dpitch, is_mirror, call)
+                if keep is not None or not is_mirror:
+                    self.ctx.synchronize()
             nsource = min((nd - 1)*self.hop + self.nfft, len(source))
             if nsource >= self.nfft:
                 self.frequencies = np.arange(F)*self.source.rate/self.nfft
@@ -186,12 +183,11 @@ class BufferedSpectrogram(BufferedData):
         (src/audian/specitem.py:36), computed on the device from the mirror when it is
         valid; returns a (F, frames) float32 host array."""
         from . import hipdsp
-        from .buffereddata import _covers
         n = len(self._hostbuf)
         F = self.nfft//2 + 1
         if n == 0:
             return np.zeros((F, 0), dtype=np.float32)
-        if self._dev is not None and _covers(self._dev_valid, 0, n):
+        if self._mirror_valid(0, n):
             img = hipdsp.DeviceArray(self.ctx, (F, n), np.float32)
             hipdsp.decibel_image(self.ctx, self._dev.view(channel*n*F, (1,)), img, n, F,
                                  ref_power, min_power)
@@ -206,7 +202,6 @@ class BufferedSpectrogram(BufferedData):
         SpecItem.update_plot shows it (src/audian/specitem.py:36).  Device reduction when the
         mirror is valid, so only (F, ceil((stop-start)/step)) float32 values cross PCIe."""
         from . import hipdsp
-        from .buffereddata import _covers
         a, b = int(start) - self.offset, int(stop) - self.offset
         n = len(self._hostbuf)
         F = self.nfft//2 + 1
@@ -215,7 +210,7 @@ class BufferedSpectrogram(BufferedData):
         ncols = (b - a + step - 1)//step
         if ncols == 0:
             return np.zeros((F, 0), dtype=np.float32)
-        if self._dev is not None and _covers(self._dev_valid, a, b):
+        if self._mirror_valid(a, b):
             img = hipdsp.DeviceArray(self.ctx, (F, ncols), np.float32)
             hipdsp.decibel_image_decimate(self.ctx, self._dev.view(channel*n*F, (1,)), img, n, F, a, b, step,
                                           ref_power, min_power)
@@ -230,13 +225,12 @@ class BufferedSpectrogram(BufferedData):
         decibel(mean over frames), floored at -200 dB.  Device reduction when the mirror is
         valid; returns float64 (F,)."""
         from . import hipdsp
-        from .buffereddata import _covers
         F = self.nfft//2 + 1
         a, b = int(i0) - self.offset, int(i1) - self.offset
         n = len(self._hostbuf)
         if a < 0 or b > n or b <= a:
             raise IndexError('range outside the loaded buffer')
-        if self._dev is not None and _covers(self._dev_valid, a, b):
+        if self._mirror_valid(a, b):
             out = hipdsp.DeviceArray(self.ctx, (F,), np.float32)
             hipdsp.mean_spectrum_db(self.ctx, self._dev.view(channel*n*F, (1,)), F, a, b, out,
                                     floor_db=floor_db)
@@ -252,7 +246,6 @@ class BufferedSpectrogram(BufferedData):
         With a valid device mirror one pass over the slab serves all bands (hipdsp_band_power, 16 bands per launch):
         a bin that lies in several bands is read once and only the result crosses PCIe."""
         from . import hipdsp
-        from .buffereddata import _covers
         F = self.nfft//2 + 1
         a, b = int(i0) - self.offset, int(i1) - self.offset
         n = len(self._hostbuf)
@@ -262,7 +255,7 @@ class BufferedSpectrogram(BufferedData):
         m = b - a
         if m == 0 or not bins:
             return np.zeros((len(bins), self.channels, m), dtype=np.float32)
-        if self._dev is not None and _covers(self._dev_valid, a, b):
+        if self._mirror_valid(a, b):
             out = hipdsp.DeviceArray(self.ctx, (len(bins), self.channels, m), np.float32)
             for j in range(0, len(bins), 16):
                 hipdsp.band_power(self.ctx, self._dev.view(a*F, (1,)), self._pitch(), self.channels, m, F,
@@ -282,11 +275,10 @@ class BufferedSpectrogram(BufferedData):
         if not self.init or len(self._hostbuf) == 0 or len(self._hostbuf.shape) < 3:
             return None, None
         from . import hipdsp
-        from .buffereddata import _covers
         F = self._hostbuf.shape[2]
         n = len(self._hostbuf)
         nf = max(F//16, 1)                       # top 1/16 of the band
-        if self._dev is not None and _covers(self._dev_valid, 0, n) and self._stale:
+        if self._mirror_valid(0, n) and self._stale:
             # everything on the device: the two order statistics np.percentile(.., 95) interpolates between
             # (radix select over the top band) and the maximum; three floats cross PCIe.  decibel() is
             # monotonic, so the percentile of the dB values is the interpolation of their dB.

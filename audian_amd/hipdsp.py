@@ -3,6 +3,7 @@ plans and the hot-path calls.  Device-native layout is planar float32
 (channels, frames); see ``include/hip_dsp.h``.
 """
 
+import contextlib
 import ctypes
 
 import numpy as np
@@ -11,7 +12,47 @@ from . import _lib
 from ._lib import check, lib
 
 
-class Context:
+class _Handle:
+    """Owns one C handle `_h`: close() destroys it once (_destroy, the subclass's), __del__ swallows errors."""
+
+    _h = None
+
+    @property
+    def handle(self):
+        return self._h
+
+    def close(self):
+        if self._h is not None and self._h.value:
+            self._destroy()
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _Memory:
+    """Owns the block at `ptr` unless `_own` is False: free() releases it once (_release, the subclass's), __del__
+    swallows errors."""
+
+    ptr = 0
+    _own = True
+
+    def free(self):
+        if self._own and self.ptr:
+            self._release()
+            self.ptr = 0
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class Context(_Handle):
     """A device + HIP stream on which libhip_dsp enqueues its work."""
 
     def __init__(self, device=0, stream=None):
@@ -20,9 +61,8 @@ class Context:
         self._h = h
         self.device = int(device)
 
-    @property
-    def handle(self):
-        return self._h
+    def _destroy(self):
+        lib.hipdsp_ctx_destroy(self._h)
 
     def set_stream(self, stream):
         check(lib.hipdsp_ctx_set_stream(self._h, ctypes.c_void_p(stream or 0)))
@@ -95,16 +135,6 @@ class Context:
     def destroy_event(self, ev):
         check(lib.hipdsp_event_destroy(self._h, ev))
 
-    def close(self):
-        if self._h is not None and self._h.value:
-            lib.hipdsp_ctx_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 _default_ctx = None
@@ -119,7 +149,7 @@ def default_context():
     return _default_ctx
 
 
-class DeviceArray:
+class DeviceArray(_Memory):
     """A caller-owned block of HBM with a NumPy-like shape/dtype (C-contiguous)."""
 
     def __init__(self, ctx, shape, dtype=np.float32, ptr=None, owner=None, write_probe=0):
@@ -173,16 +203,8 @@ class DeviceArray:
             raise ValueError('view exceeds the parent array')
         return v
 
-    def free(self):
-        if self._own and self.ptr:
-            lib.hipdsp_free(self.ctx.handle, ctypes.c_void_p(self.ptr))
-            self.ptr = 0
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+    def _release(self):
+        lib.hipdsp_free(self.ctx.handle, ctypes.c_void_p(self.ptr))
 
 
 def _p(x):
@@ -196,7 +218,7 @@ def _p(x):
     return ctypes.c_void_p(int(x))
 
 
-class SosPlan:
+class SosPlan(_Handle):
     """Device-resident plan for one SOS table (see hipdsp_sosplan_* in hip_dsp.h)."""
 
     def __init__(self, ctx, sos=None):
@@ -236,23 +258,11 @@ class SosPlan:
         check(lib.hipdsp_sosplan_info(self.ctx.handle, self._h, ctypes.byref(w), ctypes.byref(e)))
         return int(w.value), int(e.value)
 
-    @property
-    def handle(self):
-        return self._h
-
-    def close(self):
-        if self._h is not None and self._h.value:
-            lib.hipdsp_sosplan_destroy(self.ctx.handle, self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _destroy(self):
+        lib.hipdsp_sosplan_destroy(self.ctx.handle, self._h)
 
 
-class FirPlan:
+class FirPlan(_Handle):
     """Device-resident taps and thresholds of up to 16 FIR kernels of one length (hipdsp_firplan_* in hip_dsp.h)."""
 
     def __init__(self, ctx, taps=None, thresholds=None):
@@ -288,23 +298,11 @@ class FirPlan:
     def upload(self):
         check(lib.hipdsp_firplan_upload(self.ctx.handle, self._h))
 
-    @property
-    def handle(self):
-        return self._h
-
-    def close(self):
-        if self._h is not None and self._h.value:
-            lib.hipdsp_firplan_destroy(self.ctx.handle, self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _destroy(self):
+        lib.hipdsp_firplan_destroy(self.ctx.handle, self._h)
 
 
-class Comm:
+class Comm(_Handle):
     """RCCL communicator behind the C ABI (hipdsp_comm_*): rank 0 calls
     `Comm.unique_id()` and ships the 128 bytes to the other ranks."""
 
@@ -326,16 +324,8 @@ class Comm:
         check(lib.hipdsp_allgather_f32(self.ctx.handle, self._h, _p(send), _p(recv),
                                        int(count_per_rank)))
 
-    def close(self):
-        if self._h is not None and self._h.value:
-            lib.hipdsp_comm_destroy(self.ctx.handle, self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _destroy(self):
+        lib.hipdsp_comm_destroy(self.ctx.handle, self._h)
 
 
 def _plan(plan):
@@ -349,6 +339,21 @@ launches = {}
 
 def _count(name):
     launches[name] = launches.get(name, 0) + 1
+
+
+@contextlib.contextmanager
+def _result(ctx, out, shape, dtype):
+    """The device array a call writes its result into: `out` when the caller gave one (it is filled and returned as it
+    is), else a temporary of `shape` (None: nothing to write, no array) that is read back inside the block and freed
+    at its end, also when the call fails."""
+    dev = out
+    if out is None and shape is not None:
+        dev = DeviceArray(ctx, shape, dtype)
+    try:
+        yield dev
+    finally:
+        if out is None and dev is not None:
+            dev.free()
 
 
 def sosfilt(ctx, plan, x, x_pitch, y, y_pitch, channels, frames, skip=0):
@@ -525,7 +530,7 @@ def pcm_minmax(ctx, pcm_tc, sample_bytes, frames, channels, step, scale, out_rc,
                                 int(bool(down_scale)), _p(out_rc), int(out_pitch)))
 
 
-class HostBuffer:
+class HostBuffer(_Memory):
     """Page-locked host memory (hipdsp_host_malloc) seen as a NumPy uint8 array: the source of
     hipdsp_memcpy_h2d_async."""
 
@@ -540,17 +545,9 @@ class HostBuffer:
         else:
             self.array = np.zeros(0, dtype=np.uint8)
 
-    def free(self):
-        if self.ptr:
-            self.array = None
-            lib.hipdsp_host_free(self.ctx.handle, ctypes.c_void_p(self.ptr))
-            self.ptr = 0
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+    def _release(self):
+        self.array = None
+        lib.hipdsp_host_free(self.ctx.handle, ctypes.c_void_p(self.ptr))
 
 
 def memcpy_h2d_async(ctx, dst, host_src, nbytes):
@@ -602,15 +599,13 @@ def region_stats(ctx, x, x_pitch, channels, frames, regions, out=None):
     regions = [(int(a), int(b)) for a, b in regions]
     start = (ctypes.c_int64*max(1, len(regions)))(*[r[0] for r in regions])
     stop = (ctypes.c_int64*max(1, len(regions)))(*[r[1] for r in regions])
-    dev = out if out is not None else DeviceArray(ctx, (max(1, len(regions)), max(1, int(channels)), 8), np.float64)
-    _count('region_stats')
-    check(lib.hipdsp_region_stats(ctx.handle, _p(x), int(x_pitch), int(channels), int(frames), start, stop,
-                                  len(regions), _p(dev)))
-    if out is not None:
-        return out
-    res = dev.to_host()[:len(regions), :int(channels)] if int(channels) > 0 else np.zeros((len(regions), 0, 8))
-    dev.free()
-    return res
+    with _result(ctx, out, (max(1, len(regions)), max(1, int(channels)), 8), np.float64) as dev:
+        _count('region_stats')
+        check(lib.hipdsp_region_stats(ctx.handle, _p(x), int(x_pitch), int(channels), int(frames), start, stop,
+                                      len(regions), _p(dev)))
+        if out is not None:
+            return out
+        return dev.to_host()[:len(regions), :int(channels)] if int(channels) > 0 else np.zeros((len(regions), 0, 8))
 
 
 SPECTRA_GROUP = 16                      # frames per work item of hipdsp_region_spectra (csrc/regionspectra.hip: SP_GROUP)
@@ -710,18 +705,14 @@ def region_crossings(ctx, x, x_pitch, channels, frames, regions, thresholds, out
     thr = np.ascontiguousarray(np.broadcast_to(np.asarray(thresholds, dtype=np.float64), (len(tab),)))
     if len(thr) == 0:
         thr = np.zeros(1)
-    dev = out if out is not None else (DeviceArray(ctx, (len(tab), 8), np.float64) if len(tab) else None)
-    _count('region_crossings')
-    try:
+    with _result(ctx, out, (len(tab), 8) if len(tab) else None, np.float64) as dev:
+        _count('region_crossings')
         check(lib.hipdsp_region_crossings(ctx.handle, _p(x), int(x_pitch), int(channels), int(frames),
                                           tab.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
                                           thr.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), len(tab), _p(dev)))
         if out is not None:
             return out
         return dev.to_host() if dev is not None else np.zeros((0, 8))
-    finally:
-        if out is None and dev is not None:
-            dev.free()
 
 
 def detect_events_into(ctx, x, x_pitch, channels, start, stop, thresholds, min_gap, min_len, capacity, events, counts,
@@ -850,15 +841,13 @@ def histogram(ctx, x, x_pitch, channels, start, stop, edges, out=None, out_pitch
     with `out` (a DeviceArray of int64, rows `out_pitch` elements apart, 0 = B + 3), fills it and returns it."""
     e = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
     B, channels = len(e) - 1, int(channels)
-    dev = out if out is not None else DeviceArray(ctx, (max(1, channels), max(1, B) + 3), np.int64)
-    _count('histogram')
-    check(lib.hipdsp_histogram(ctx.handle, _p(x), int(x_pitch), channels, int(start), int(stop),
-                               e.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), B, _p(dev), int(out_pitch)))
-    if out is not None:
-        return out
-    res = dev.to_host()[:channels] if channels > 0 else np.zeros((0, B + 3), dtype=np.int64)
-    dev.free()
-    return res
+    with _result(ctx, out, (max(1, channels), max(1, B) + 3), np.int64) as dev:
+        _count('histogram')
+        check(lib.hipdsp_histogram(ctx.handle, _p(x), int(x_pitch), channels, int(start), int(stop),
+                                   e.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), B, _p(dev), int(out_pitch)))
+        if out is not None:
+            return out
+        return dev.to_host()[:channels] if channels > 0 else np.zeros((0, B + 3), dtype=np.int64)
 
 
 def masked_stats(ctx, x, x_pitch, channels, start, stop, bounds, out=None):
@@ -873,19 +862,17 @@ def masked_stats(ctx, x, x_pitch, channels, start, stop, bounds, out=None):
         if b.shape != (channels, 3):
             raise ValueError('bounds: (channels, 3) values lo, hi, pivot')
         dbounds = DeviceArray.from_host(ctx, b if channels > 0 else np.zeros((1, 3)))
-    dev = out if out is not None else DeviceArray(ctx, (max(1, channels), 4), np.float64)
     try:
-        _count('masked_stats')
-        check(lib.hipdsp_masked_stats(ctx.handle, _p(x), int(x_pitch), channels, int(start), int(stop), _p(dbounds),
-                                      _p(dev)))
-        if out is not None:
-            return out
-        return dev.to_host()[:channels] if channels > 0 else np.zeros((0, 4))
+        with _result(ctx, out, (max(1, channels), 4), np.float64) as dev:
+            _count('masked_stats')
+            check(lib.hipdsp_masked_stats(ctx.handle, _p(x), int(x_pitch), channels, int(start), int(stop), _p(dbounds),
+                                          _p(dev)))
+            if out is not None:
+                return out
+            return dev.to_host()[:channels] if channels > 0 else np.zeros((0, 4))
     finally:
         if dbounds is not bounds:
             dbounds.free()
-        if out is None:
-            dev.free()
 
 
 def memcpy2d(ctx, dst, dst_pitch_bytes, src, src_pitch_bytes, width_bytes, height):

@@ -5,7 +5,7 @@ trace -- channel-group means, optional heterodyne (multiply by a sine carrier, z
 
 import numpy as np
 
-from .buffereddata import BufferedData, _covers
+from .buffereddata import BufferedData
 from .design import butter_sos
 
 
@@ -29,8 +29,7 @@ def play_data(trace, t0, t1, show_channels, heterodyne_freq=None):
         groups.append(list(show_channels[n2:]))
     trace.update_buffer(i0, i1)
     a = i0 - trace.offset
-    on_device = isinstance(trace, BufferedData) and trace._dev is not None and \
-        _covers(trace._dev_valid, a, a + n) and n > 0
+    on_device = isinstance(trace, BufferedData) and trace._mirror_valid(a, a + n) and n > 0
     if not on_device:
         data = trace[i0:i1, :]
         play = np.zeros((n, len(groups)))

@@ -380,3 +380,161 @@ def test_load_geometry_is_what_process_gets(seed):
         g.update_times(t0, min(span, t0 + float(rng.uniform(0.01, 0.3))*span))
     t.recompute_all()
     assert len(t.calls) >= 2
+
+
+# ---- process() of the traces that have a numpy definition, on plain arrays -----------------------------------------------
+
+NBEFORE, SLAB, CH = 3, 64, 3
+
+
+def _host_cases():
+    """name -> (trace, source slab, dest, what the class's own host definition gives)."""
+    from audian_amd.bufferedbandpower import BufferedBandPower
+    from audian_amd.bufferedcommonreference import BufferedCommonReference, common_reference_host
+    from audian_amd.bufferedeventfilter import BufferedEventFilter
+    from audian_amd.bufferedkernelfilter import BufferedKernelFilter, fir_same
+    from audian_amd.bufferedlowpass import BufferedLowpass
+    from audian_amd.bufferedpowerenvelope import BufferedPowerEnvelope, power_envelope_host
+    from audian_amd.design import butter_sos
+    from audian_amd.refine import host_region_filtfilt
+    rng = np.random.default_rng(5)
+    x = rng.standard_normal((SLAB, CH))
+    n = SLAB - NBEFORE
+    cases = {}
+
+    spec = rng.random((SLAB, CH, 9))
+    t = BufferedBandPower()
+    t.k0, t.k1, t.scale = 2, 5, 0.5
+    cases['bandpower'] = (t, spec, np.zeros((n, CH)), 0.5*np.sum(spec[NBEFORE:, :, 2:5], axis=2))
+
+    t = BufferedKernelFilter(kernel=[0.25, 0.5, 0.25], step=2, threshold=0.1)
+    m = -(-n//2)
+    cases['kernelfilter'] = (t, x, np.zeros((m, CH)),
+                             np.maximum(fir_same(x, [0.25, 0.5, 0.25], NBEFORE, 2, m) - 0.1, 0.0))
+
+    cases['eventfilter'] = (BufferedEventFilter(), x, np.zeros((n, CH)), x[NBEFORE:])
+
+    t = BufferedLowpass(cutoff=50.0)
+    t.rate = 1000.0
+    sos = butter_sos(1, 50.0, 'lowpass', 1000.0)
+    want = np.stack([host_region_filtfilt(x[:, c], sos)[NBEFORE:] for c in range(CH)], axis=1)
+    cases['lowpass'] = (t, x, np.zeros((n, CH)), want)
+
+    t = BufferedPowerEnvelope(step=4)
+    t.step, t.sos = 4, sos
+    m = -(-n//4)
+    cases['powerenvelope'] = (t, x, np.zeros((m, CH)), power_envelope_host(sos, x, NBEFORE, 4, m, 4.0, True))
+
+    t = BufferedCommonReference(method='median')
+    t.group, t.use = np.array([0, 0, -1], dtype=np.int32), np.ones(CH, dtype=bool)
+    cases['commonreference'] = (t, x, np.zeros((n, CH)), common_reference_host(x[NBEFORE:], t.group, t.use, 'median'))
+    for t, *_ in cases.values():
+        t.channels = CH
+        t.source = BufferedData('upstream', 'data')          # a derived source without a mirror: the host path
+    return cases
+
+
+@pytest.mark.parametrize('name', ['bandpower', 'kernelfilter', 'eventfilter', 'lowpass', 'powerenvelope',
+                                  'commonreference'])
+def test_process_on_plain_arrays_and_its_host_tail(name):
+    """process() called directly (no _pending) computes the class's numpy definition and leaves _dev_valid and _stale
+    alone; called for a slab of the buffer (a _pending over [doffset, doffset + dnframes)) it computes the same and takes
+    exactly that range out of both.  No device context is created: the source has no mirror."""
+    from audian_amd.buffereddata import _Call
+    t, source, dest, want = _host_cases()[name]
+    assert t._pending is None and t._ctx is None
+    t._dev_valid, t._stale = [[0, 100]], [[10, 90]]
+    t.process(source, dest, NBEFORE)
+    assert np.array_equal(dest, want)
+    assert t._dev_valid == [[0, 100]] and t._stale == [[10, 90]]
+    dest[...] = np.nan
+    t._pending = _Call(7, len(source), 20, len(dest))
+    t.process(source, dest, NBEFORE)
+    assert np.array_equal(dest, want)
+    n = len(dest)
+    assert t._pending is None
+    assert t._dev_valid == [[0, 20], [20 + n, 100]] and t._stale == [[10, 20], [20 + n, 90]]
+    assert t._ctx is None and t._dev is None
+    # a dest that does not fit raises numpy's error before anything is touched
+    t._pending = _Call(7, len(source), 20, n + 1)
+    with pytest.raises(ValueError, match=r'could not broadcast input array from shape \(%d,\) into shape \(%d,\)'
+                       % (n, n + 1)):
+        t.process(source, np.zeros((n + 1,) + dest.shape[1:]), NBEFORE)
+
+
+# ---- the range checks every analysis call goes through -----------------------------------------------------------------
+
+_IDENTITY = [[1.0, 0.0, 0.0, 1.0, 0.0, 0.0]]
+RANGE_CALLS = {
+    'detect_events': lambda t, a, b: t.detect_events(0.5, start=a, stop=b),
+    'find_peaks': lambda t, a, b: t.find_peaks(start=a, stop=b),
+    'histogram': lambda t, a, b: t.histogram([0.0, 1.0, 2.0], a, b),
+    'masked_stats': lambda t, a, b: t.masked_stats(0.0, 1.0, None, a, b),
+    'threshold_estimates': lambda t, a, b: t.threshold_estimates(a, b),
+}
+TABLE_CALLS = {
+    'region_spectra': lambda t, regions: t.region_spectra(regions, 16),
+    'region_filtfilt': lambda t, regions: t.region_filtfilt(regions, np.array([_IDENTITY]*len(regions))),
+    'region_crossings': lambda t, regions: t.region_crossings(regions, 0.5),
+}
+
+
+def _loader():
+    a = ArrayLoader(ramp(1000), 100.0, buffer_time=2.0, back_time=0.5)
+    a.update_buffer(400, 500)
+    assert (a.offset, len(a.buffer)) == (350, 200)
+    return a
+
+
+@pytest.mark.parametrize('name', sorted(RANGE_CALLS))
+def test_trace_range_callers(name):
+    call = RANGE_CALLS[name]
+    for a, b in ((300, 400), (500, 551), (450, 440)):
+        with pytest.raises(IndexError, match='range outside the loaded buffer'):
+            call(_loader(), a, b)
+    t = _loader()
+    t.shape = (1000, 2, 5)
+    with pytest.raises(TypeError, match='%s is for traces, not for spectrogram-shaped data' % name):
+        call(t, 400, 500)
+    with pytest.raises(TypeError):                    # the kind of data is checked before the range
+        call(t, 300, 400)
+
+
+def test_a_bad_channel_of_a_range_call():
+    with pytest.raises(IndexError):
+        _loader().histogram([0.0, 1.0, 2.0], 400, 500, channel=2)
+    with pytest.raises(ValueError, match='thresholds: one value or one per channel'):
+        _loader().detect_events([0.5, 0.5, 0.5], start=400, stop=500)
+    with pytest.raises(IndexError):                   # the range is checked before the thresholds
+        _loader().detect_events([0.5, 0.5, 0.5], start=300, stop=400)
+
+
+@pytest.mark.parametrize('name', sorted(TABLE_CALLS))
+def test_region_table_callers(name):
+    call = TABLE_CALLS[name]
+    for regions in ([(0, 300, 400)], [(0, 400, 500), (1, 500, 551)], [(1, 450, 440)]):
+        with pytest.raises(IndexError, match='range outside the loaded buffer'):
+            call(_loader(), regions)
+    for regions in ([(2, 400, 500)], [(0, 400, 500), (-1, 400, 500)]):
+        with pytest.raises(IndexError, match='channel outside the trace'):
+            call(_loader(), regions)
+    with pytest.raises(IndexError, match='channel outside the trace'):      # the channel before the range
+        call(_loader(), [(2, 300, 400)])
+    t = _loader()
+    t.shape = (1000, 2, 5)
+    with pytest.raises(TypeError, match='%s is for traces, not for spectrogram-shaped data' % name):
+        call(t, [(2, 300, 400)])
+
+
+def test_region_spectra_checks_in_their_order():
+    """The kind of data, then nfft and hop, then the table."""
+    t = _loader()
+    with pytest.raises(ValueError, match='nfft 12 is not a power of two'):
+        t.region_spectra([(2, 300, 400)], 12)
+    with pytest.raises(ValueError, match='hop 17 not in'):
+        t.region_spectra([(2, 300, 400)], 16, hop=17)
+    with pytest.raises(IndexError):
+        t.region_spectra([(2, 300, 400)], 16)
+    t.shape = (1000, 2, 5)
+    with pytest.raises(TypeError):
+        t.region_spectra([(2, 300, 400)], 12)
