@@ -151,6 +151,7 @@ _SIGNATURES = {
     'hipdsp_region_spectra': ([_vp, _vp, _i64, _i64, _i64, ctypes.POINTER(_i64), _i64, _int, _int, _i64, _dbl, _vp, _i64, _vp], _int),
     'hipdsp_region_filtfilt': ([_vp, _vp, _i64, _vp, _i64, _i64, _i64, ctypes.POINTER(_i64), _i64, ctypes.POINTER(_dbl), _int, _int], _int),
     'hipdsp_region_crossings': ([_vp, _vp, _i64, _i64, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_dbl), _i64, _vp], _int),
+    'hipdsp_region_xcorr': ([_vp, _vp, _i64, _i64, _i64, ctypes.POINTER(_i64), _i64, ctypes.POINTER(_int), _int, _int, _vp, _i64, _vp], _int),
     'hipdsp_power_envelope': ([_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _dbl, _int, _vp, _i64], _int),
     'hipdsp_comm_unique_id': ([_vp], _int),
     'hipdsp_comm_create': ([_vp, _vp, _int, _int, _pp], _int),

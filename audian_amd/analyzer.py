@@ -332,3 +332,43 @@ class PeakFrequencyAnalyzer(Analyzer):
             for c in channels:
                 self.store(float(freqs[c][k]), float(powers[c][k]))
         return True
+
+
+class CrossCorrelationAnalyzer(Analyzer):
+    """The source channel of the region of one trace, how much later than the region the source carries it, and their
+    correlation (xcorr.attribute_events over BufferedArray.region_xcorr): for every region of a channel the other
+    channels are searched, over the lags of +-`max_delay` seconds, for the same waveform at least `min_ratio` times as
+    loud and correlated by at least `min_r`.  A region that is its own source stores its own channel, 0 and 1.  The two
+    thresholds are not calibrated on recordings."""
+
+    def __init__(self, graph, source_name='filtered', max_delay=0.001, min_r=0.5, min_ratio=1.0, channels=None):
+        super().__init__(graph, 'cross correlation', source_name)
+        from .xcorr import MAX_LAG
+        self.max_lag = int(round(float(max_delay)*self.source.rate))
+        if self.max_lag < 0 or self.max_lag > MAX_LAG:
+            raise ValueError('max_delay %g s is %d frames: at most %d' % (max_delay, self.max_lag, MAX_LAG))
+        self.min_r, self.min_ratio, self.channels = float(min_r), float(min_ratio), channels
+        nd = max(0, int(floor(-log10(1/self.source.rate))))
+        self.make_column('source channel', '', '%.0f')
+        self.make_column('delay', 's', f'%.{nd}f')
+        self.make_column('correlation', '', '%.3f')
+
+    def _attribute(self, table):
+        from .xcorr import attribute_table
+        trace = self.source
+        if table:
+            trace.update_buffer(min(a for c, a, b in table), max(b for c, a, b in table))
+        return attribute_table(trace.region_xcorr(table, self.channels, self.max_lag), self.min_r, self.min_ratio)
+
+    def analyze(self, t0, t1, channel, traces):
+        i0, i1 = self.graph.region_frames(self.source, t0, t1)
+        src, delay, corr = self._attribute([(channel, i0, i1)])
+        self.store(int(src[0]), float(delay[0]), float(corr[0]))
+
+    def analyze_many(self, regions, channels):
+        spans = [self.graph.region_frames(self.source, t0, t1) for t0, t1 in regions]
+        # one device call for all regions and channels, the rows in region-major order
+        src, delay, corr = self._attribute([(c, a, b) for a, b in spans for c in channels])
+        for k in range(len(src)):
+            self.store(int(src[k]), float(delay[k]), float(corr[k]))
+        return True

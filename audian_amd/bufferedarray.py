@@ -327,7 +327,7 @@ class BufferedArray(object):
 
     def _region_table(self, regions, what):
         """(R, 3) int64 table of channel, start, stop relative to the buffer of a region_spectra / region_filtfilt /
-        region_crossings call."""
+        region_crossings / region_xcorr call."""
         self._require_trace(what)
         tab = np.asarray([(int(c), int(a), int(b)) for c, a, b in regions], dtype=np.int64).reshape(-1, 3)
         if len(tab) and (tab[:, 0].min() < 0 or tab[:, 0].max() >= self.channels):
@@ -394,6 +394,39 @@ class BufferedArray(object):
             res[i] = host_region_crossings(np.asarray(buf[a:b, c], dtype=np.float32), 0, b - a, thr[i])
             res[i, [2, 3, 5]] += np.where(res[i, [2, 3, 5]] >= 0, a + self.offset, 0)
         return res
+
+    def _xcorr_arguments(self, regions, partners, max_lag):
+        """((R, 3) int64 table relative to the buffer, partner channels, max_lag) of a region_xcorr call."""
+        from .xcorr import MAX_LAG
+        tab = self._region_table(regions, 'region_xcorr')
+        L = int(max_lag)
+        if L < 0 or L > MAX_LAG or L != max_lag:
+            raise ValueError('max_lag %r is not a whole number of frames in [0, %d]' % (max_lag, MAX_LAG))
+        partners = list(range(self.channels)) if partners is None else [int(p) for p in partners]
+        if any(p < 0 or p >= self.channels for p in partners):
+            raise ValueError('partner channel outside the trace')
+        return tab, partners, L
+
+    def region_xcorr(self, regions, partners=None, max_lag=0):
+        """The correlation coefficient of frames [start, stop) (absolute, inside the current buffer) of one channel with
+        the frames [start + l, stop + l) of every channel of `partners` (None: every channel; the region's own channel
+        and repeats are allowed), for every (channel, start, stop) of `regions` and every lag l in [-max_lag, max_lag]
+        (at most 1024), with numpy on the host buffer: np.corrcoef per lag on the float32 samples, NaN where the shifted
+        window leaves the buffer, where a window is constant or holds a NaN or an infinity (xcorr.host_region_xcorr; the
+        definition: hipdsp_region_xcorr in include/hip_dsp.h; BufferedData.region_xcorr is the same on the device
+        mirror).  A positive lag: the partner carries the waveform later.  TypeError for spectrogram-shaped traces,
+        ValueError for a bad lag or partner.  Returns a CrossCorrelation object."""
+        from .xcorr import CrossCorrelation, host_region_xcorr
+        tab, partners, L = self._xcorr_arguments(regions, partners, max_lag)
+        r = np.full((len(tab), len(partners), 2*L + 1), np.nan, dtype=np.float32)
+        info = np.zeros((len(tab), len(partners), 4))
+        buf = self.buffer
+        for i, (c, a, b) in enumerate(tab):
+            row = np.asarray(buf[:, c], dtype=np.float32)
+            for j, p in enumerate(partners):
+                r[i, j], info[i, j] = host_region_xcorr(row, np.asarray(buf[:, p], dtype=np.float32), int(a), int(b), L)
+        tab[:, 1:] += self.offset
+        return CrossCorrelation(tab, partners, r, info, L, self.rate, getattr(self, 'name', None))
 
     def peak_freqs(self, events, freq_resolution, min_nfft=16, max_nfft=8192, thresh=None, step=1, powers=False):
         """The main spectral peak of every event in Hz -- env_freqs of the reference's songdetector.py

@@ -749,6 +749,40 @@ class BufferedData(BufferedArray):
         finally:
             tmp.free()
 
+    def region_xcorr(self, regions, partners=None, max_lag=0, max_bytes=2**30):
+        """BufferedArray.region_xcorr on the device mirror when it is valid over every region WIDENED by max_lag frames on
+        both sides, as far as the buffer reaches -- the partners are read there; lags whose window leaves the buffer stay
+        NaN, a lag that would leave the valid part of the mirror sends the whole call to the host: ONE hipdsp_region_xcorr
+        call for all regions and partners; 4*(2 max_lag + 1) + 32 bytes per region and partner come back.  A table whose
+        rows and scratch (hipdsp.region_xcorr_scratch) would take more than `max_bytes` is split, in its order, into
+        calls that stay under it -- the same bytes as one call, a row does not depend on what rides with it.  Else numpy
+        on the host buffer.  Nothing is read back from the mirror: the host copy stays as stale as it was.  Returns a
+        CrossCorrelation object."""
+        from . import hipdsp
+        from .xcorr import CrossCorrelation
+        tab, partners, L = self._xcorr_arguments(regions, partners, max_lag)
+        n = len(self._hostbuf)
+        # what the call reads: an empty region reads nothing, but _regions_on_mirror asks for its (empty) range as it is
+        reach = np.array([(c, max(a - L, 0), min(b + L, n)) if b > a else (c, a, b) for c, a, b in tab.tolist()],
+                         dtype=np.int64).reshape(-1, 3)
+        if not self._regions_on_mirror(reach) or not partners:
+            return BufferedArray.region_xcorr(self, [(c, a + self.offset, b + self.offset) for c, a, b in tab.tolist()],
+                                              partners, max_lag)
+        P, W = len(partners), 2*L + 1
+        # the bytes of a call grow by this much with every region: its row of the table, its partial rows, its results
+        base = hipdsp.region_xcorr_scratch(tab[:0], P, L)
+        each = [hipdsp.region_xcorr_scratch(tab[i:i + 1], P, L) - base + P*(4*W + 32) for i in range(len(tab))]
+        r, info, first, used = np.zeros((len(tab), P, W), dtype=np.float32), np.zeros((len(tab), P, 4)), 0, base
+        for i in range(len(tab) + 1):
+            if i == len(tab) or (i > first and used + each[i] > max_bytes):
+                r[first:i], info[first:i] = hipdsp.region_xcorr(self.ctx, self._dev, self._pitch(), self.channels, n,
+                                                                tab[first:i], partners, L)
+                first, used = i, base
+            if i < len(tab):
+                used += each[i]
+        tab[:, 1:] += self.offset
+        return CrossCorrelation(tab, partners, r, info, L, self.rate, self.name)
+
     def region_crossings(self, regions, thresholds):
         """BufferedArray.region_crossings on the device mirror when it is valid over every region: ONE
         hipdsp_region_crossings call, 64 bytes per region come back.  Nothing is read back from the mirror."""

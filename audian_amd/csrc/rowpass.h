@@ -1,7 +1,8 @@
-// What the analysis units (regionstats, histogram, events, peaks, regionspectra, regionfilter) share: the 16-byte-phased
-// chunk a thread holds in registers, wave reductions, the exclusive scan of one channel's [chunk] array, the four-wave sum and
-// the finish of the two shifted moments, the owner lookup of a region table; on the host the row-range checks, the intake of a
-// (channel, start, stop) table and the carving of the context scratch.  Every piece has at least two users.
+// What the analysis units (regionstats, histogram, events, peaks, regionspectra, regionfilter, regionxcorr) share: the
+// 16-byte-phased chunk a thread holds in registers, wave reductions, the exclusive scan of one channel's [chunk] array, the
+// four-wave sum and the finish of the two shifted moments, the owner lookup of a region table; on the host the row-range
+// checks, the intake of a (channel, start, stop) table and the carving of the context scratch.  Every piece has at least two
+// users.
 #pragma once
 #include "common.h"
 #include <cmath>

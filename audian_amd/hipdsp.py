@@ -641,6 +641,57 @@ def region_spectra(ctx, x, x_pitch, channels, frames, regions, nfft, hop, step, 
         info.free()
 
 
+XCORR_TILE = 2048                       # samples of hipdsp_region_xcorr staged at a time (csrc/regionxcorr.hip: XC_TILE)
+XCORR_CHUNK = 32*XCORR_TILE             # samples per work item of it (XC_CHUNK), anchored at the region's start
+XCORR_LAGS = 9                          # consecutive lags a thread owns (XC_RL)
+XCORR_MAX_LAG = 1024
+
+
+def region_xcorr_scratch(regions, n_partners, max_lag):
+    """Bytes of context scratch one hipdsp_region_xcorr call over these regions takes (the formula of include/hip_dsp.h)."""
+    tab = np.asarray(regions, dtype=np.int64).reshape(-1, 3)
+    items = int(n_partners)*int(((tab[:, 2] - tab[:, 1] + XCORR_CHUNK - 1)//XCORR_CHUNK).sum())
+    tables = -(-(48*(len(tab) + 1) + 4*int(n_partners))//8)*8          # the float64 rows behind them start at a multiple of 8
+    return tables + 8*(4 + 3*XCORR_LAGS*(-(-(2*int(max_lag) + 1)//XCORR_LAGS)))*items
+
+
+def region_xcorr_into(ctx, x, x_pitch, channels, frames, regions, partners, max_lag, out, info, out_pitch=0):
+    """One hipdsp_region_xcorr launch, the results staying on the device: `out` (len(regions), len(partners), 2 max_lag +
+    1) float32 and `info` (len(regions), len(partners), 4) float64 are DeviceArrays; `regions` is an (n, 3) int64 host
+    table of channel, start, stop, `partners` a host list of channel ids."""
+    tab = np.ascontiguousarray(regions, dtype=np.int64).reshape(-1, 3)
+    par = np.ascontiguousarray(partners, dtype=np.intc).reshape(-1)
+    _count('region_xcorr')
+    check(lib.hipdsp_region_xcorr(ctx.handle, _p(x), int(x_pitch), int(channels), int(frames),
+                                  tab.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), len(tab),
+                                  par.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), len(par), int(max_lag), _p(out),
+                                  int(out_pitch), _p(info)))
+
+
+def region_xcorr(ctx, x, x_pitch, channels, frames, regions, partners, max_lag):
+    """Correlation coefficients of x[channel, start:stop] with x[p, start+l:stop+l] for every (channel, start, stop) of
+    `regions`, every p of `partners` and every lag l in [-max_lag, max_lag] (hipdsp_region_xcorr: np.corrcoef per lag, NaN
+    where the shifted window leaves the row; a positive peak lag: the partner carries the waveform later).  Returns the
+    (len(regions), len(partners), 2 max_lag + 1) float32 rows and the (len(regions), len(partners), 4) float64 array of
+    the number of lags with a value, the position of the largest, std of the event window and of the partner's there."""
+    tab = np.ascontiguousarray(regions, dtype=np.int64).reshape(-1, 3)
+    par = np.ascontiguousarray(partners, dtype=np.intc).reshape(-1)
+    n, P, W = len(tab), len(par), 2*int(max_lag) + 1
+    if n == 0 or P == 0:
+        region_xcorr_into(ctx, x, x_pitch, channels, frames, tab, par, max_lag, None, None)
+        return np.zeros((n, P, max(W, 0)), dtype=np.float32), np.zeros((n, P, 4), dtype=np.float64)
+    if W < 1:
+        raise ValueError('max_lag %d is negative' % int(max_lag))
+    out = DeviceArray(ctx, (n, P, W), np.float32)
+    info = DeviceArray(ctx, (n, P, 4), np.float64)
+    try:
+        region_xcorr_into(ctx, x, x_pitch, channels, frames, tab, par, max_lag, out, info)
+        return out.to_host(), info.to_host()
+    finally:
+        out.free()
+        info.free()
+
+
 FILTER_CHUNK = 64                       # samples per hand-over of hipdsp_region_filtfilt (csrc/regionfilter.hip: RF_CHUNK),
 #                                         anchored at the first sample of a region's extended sequence
 FILTER_TILE = 64*FILTER_CHUNK           # samples per wave of it: 64 consecutive chunks staged together

@@ -224,6 +224,35 @@ class TraceGraph(object):
                                  for c in range(events.channels)], trace.rate, trace.name)
         return trace.peak_freqs(events, freq_resolution, min_nfft, max_nfft, thresh, step)
 
+    def event_cross_correlation(self, events, trace_name=None, max_delay=0.001, channels=None):
+        """The correlation of every event with the other channels over the lags of +-`max_delay` seconds, taken on
+        `trace_name` (by default the trace the events were detected on): what tells an animal's own song from its
+        crosstalk on the neighbouring microphones (xcorr.py).  max_lag = round(max_delay * rate) frames, at most 1024.
+        The buffers are moved as in event_peak_freqs so that the trace holds all events, then the trace computes
+        (BufferedData.region_xcorr: on its device mirror when it has one, ONE call for all events and partners).
+        `channels`: the partner channels, by default all.  Returns ONE CrossCorrelation over all events, channel by
+        channel in the events' order (xcorr.event_table); a positive lag: the partner carries the event later."""
+        from .xcorr import MAX_LAG, event_table
+        trace = self[events.trace_name if trace_name is None else trace_name]
+        max_lag = int(round(float(max_delay)*trace.rate))
+        if max_lag < 0 or max_lag > MAX_LAG:
+            raise ValueError('max_delay %g s is %d frames of %s: at most %d frames (%g s) to either side'
+                             % (max_delay, max_lag, trace.name, MAX_LAG, MAX_LAG/trace.rate))
+        table = event_table(events, trace.rate/events.rate)
+        if len(table):
+            a, b = int(table[:, 1].min()), int(table[:, 2].max())
+            if a < trace.offset or b > trace.offset + len(trace._buf()):
+                self._event_frames(trace, (a + 0.5)/trace.rate, (b - 0.5)/trace.rate)       # as Events.regions
+        return trace.region_xcorr(table, channels, max_lag)
+
+    def attribute_events(self, events, trace_name=None, max_delay=0.001, channels=None, min_r=0.5, min_ratio=1.0):
+        """event_cross_correlation followed by the attribution rule (xcorr.attribute_events, whose two thresholds are
+        not calibrated on recordings): returns (own, sources, delays) -- the Events that are their own source, and per
+        channel the source channel of ALL events and the source's delay in seconds."""
+        from .xcorr import attribute_events
+        xc = self.event_cross_correlation(events, trace_name, max_delay, channels)
+        return attribute_events(events, xc, min_r, min_ratio)
+
     def clean_event_freqs(self, events, freqs, fac=6.0):
         """clean_env_freqs of the reference's songdetector.py (songdetector.py:155-175, called at :763): frequencies
         further than fac standard deviations from the mean of the pooled frequencies' middle half become NaN, and

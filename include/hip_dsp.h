@@ -994,6 +994,78 @@ int hipdsp_region_filtfilt(hipdsp_ctx *ctx, const float *x, int64_t x_pitch, flo
 int hipdsp_region_crossings(hipdsp_ctx *ctx, const float *x, int64_t x_pitch, int64_t channels, int64_t frames,
                             const int64_t *host_regions, const double *host_thresholds, int64_t n_regions, double *out);
 
+/* The windowed cross-correlation coefficient of many regions against a list of partner channels, over the lags -L ... L:
+ * which channel an event belongs to and how much later it arrives elsewhere.  The reference has no code for this; its
+ * songdetector.py ends on the problem ("crosstalk in front of songs in trace 0").  The contract is pinned to numpy.
+ * x and host_regions are as in hipdsp_region_spectra: planar float32, `channels` rows of `frames` valid elements, x_pitch
+ * apart (0 = frames); a HOST array (n_regions, 3) of int64 channel, start, stop with 0 <= channel < channels and 0 <= start
+ * <= stop <= frames.  Regions may overlap or repeat; an empty region is allowed.  host_partners is a HOST list of n_partners
+ * channel ids in [0, channels); repeats are allowed, and so is the region's own channel.  L = max_lag, 0 <= L <= 1024, W =
+ * 2 L + 1.  out is a DEVICE array (n_regions, n_partners, W) float32, its rows out_pitch elements apart (0 = W); info is a
+ * DEVICE array (n_regions, n_partners, 4) float64, compact.
+ * For region (c, start, stop), partner p and lag l in [-L, L], with n = stop - start, a = float64(x[c, start:stop]) and
+ * b_l = float64(x[p, start+l : stop+l]):
+ *   lag l is VALID iff n >= 1, start + l >= 0 and stop + l <= frames.  An invalid lag gives out[.., L + l] = NaN; no
+ *   sample outside [0, frames) of a row is ever read.
+ *   For a valid lag out[.., L + l] = float32(clamp(r, -1, 1)), r = cov(a, b_l) / (std(a) std(b_l)) with population
+ *   moments: np.corrcoef(a, b_l)[0, 1].
+ *   r is NaN where the computed variance of a or of b_l is 0: a constant window (numpy gives NaN there too).
+ *   A NaN or +-inf among the samples of a makes the whole row NaN; one among the samples of b_l makes that lag NaN.
+ *   info[.., 0]  the number of lags whose value is not NaN
+ *   info[.., 1]  the position in [0, W) of the largest value that is not NaN, first occurrence, or -1
+ *   info[.., 2]  std(a); NaN for n == 0 and for a window with a NaN or +-inf
+ *   info[.., 3]  std(b_l) at the position [1], NaN when [1] is -1
+ * Sign convention: a POSITIVE peak lag means the partner carries the same waveform LATER -- x[p, i + l] ~ x[c, i] -- so
+ * the event's channel leads.
+ * Errors, all decided on the host before anything is launched or written:
+ *   HIPDSP_ERR_INVALID      a NULL argument; negative sizes; x_pitch < frames; out_pitch < W (other than 0); a region with
+ *                           its channel outside [0, channels) or its range outside [0, frames] or with stop < start; a
+ *                           partner outside [0, channels); max_lag < 0; misaligned pointers; more than 2^31 - 1 work items
+ *                           or (region, partner) pairs; a call inside hipdsp_graph_begin/end (the call reads the host
+ *                           tables and uploads them itself, waiting once for the context's stream, like
+ *                           hipdsp_region_spectra).
+ *   HIPDSP_ERR_UNSUPPORTED  max_lag > 1024.
+ * n_regions == 0 or n_partners == 0 writes nothing.
+ * Non-finite samples are carried as flags beside the sums, not left to inf - inf: a sample that is not finite enters the
+ * sums as a NaN, which no float64 sum loses, so "the window of a (of b_l) held one" is exactly "its sum of samples is NaN";
+ * the event window's flag is stored as such, a lag's is its NaN sum, and nothing else of a flagged row or lag is used.  Other
+ * lags, partners and regions are not affected.  A pivot (below) that is not finite is replaced by 0.
+ * Accuracy contract for finite input.  The sums are pivot-shifted and carried in float64, as in hipdsp_region_stats: with
+ * K_a = x[c, start], K_b = x[p, start], d = a - K_a, e = b_l - K_b (each one rounding to float64),
+ *   A1 = sum d, A2 = sum d^2, B1[l] = sum e, B2[l] = sum e^2, C[l] = sum d e        full sums per lag, fma for the products
+ *   va = max(A2/n - (A1/n)^2, 0), vb[l] likewise, cov = C/n - (A1/n)(B1/n), r = cov / (sqrt(va) sqrt(vb))
+ * For EVERY summation order, with u = 2^-53, g = (n+3)u / (1 - (n+3)u), D2 = mean d^2, E2 = mean e^2 (exact, of the exact
+ * shifted samples), sigma_a^2, sigma_b^2, cov the exact moments:
+ *     |va^ - sigma_a^2| = Ea  <= 4g*D2 + u*sigma_a^2          |vb^ - sigma_b^2| = Eb  <= 4g*E2 + u*sigma_b^2
+ *     |cov^ - cov|      = Ec  <= 4g*sqrt(D2*E2) + u*|cov|     (mean |d e| <= sqrt(D2 E2); |mean d| |mean e| likewise)
+ *     eta = (1 + Ea/sigma_a^2)(1 + Eb/sigma_b^2)(1 + u)^4 - 1                  the denominator is within 1 +- eta, eta < 1
+ *     |r^ - r| (1 + 2^-24) <= T = (1 + 2^-24) (Ec / (sigma_a sigma_b) + |r| eta) / (1 - eta)
+ * (each sum of n products carries n + 2 roundings, (1+u)^(n+2) <= 1 + g; the two means enter cov with 2g + g^2; the
+ * divisions by n, the product of the means and the subtraction add less than g between them; the clamp moves r^ only
+ * towards [-1, 1], where r lies.)  The stored value adds ONE rounding to float32, of r^: |out - r| <= 2^-24 |r^| + |r^ - r| <=
+ * 2^-24 |r| + T, which is why T carries the factor 1 + 2^-24.
+ * tests/xcorr_definition.py restates T; for every input of tests/test_gpu_region_xcorr.py T < 2^-30.  (float32 sums at n =
+ * 65536 under a DC offset are off by a hundred float32 roundings.)  info[2] and info[3] meet hipdsp_region_stats' bound on
+ * the standard deviation with Ea, Eb above; info[0] and [1] are exact functions of the stored row.
+ * Work (csrc/regionxcorr.hip): a flat list of (region, partner, chunk) items sized exactly from the table -- a chunk is
+ * 65536 consecutive samples of the event window counted from start -- one workgroup per item, so short events launch
+ * nothing for long ones.  A workgroup takes its chunk in tiles of 2048 samples: the tile of a and the 2048 + (valid lags) - 1
+ * samples of b it meets are converted and shifted ONCE and kept in LDS as float64; a thread owns 9 consecutive lags and a
+ * segment of the tile and feeds 27 float64 accumulators from registers.  Only the valid lags are staged and computed: the
+ * cost follows the lags asked for.  A second launch, one workgroup per (region, partner), adds the chunks in ascending
+ * order and forms the row and its info.  Per partner each sample of a is read once and each sample of b (2048 + valid lags - 1) / 2048 times.
+ * Uses the context scratch: 48 * (n_regions + 1) + 4 * n_partners bytes (the tables), rounded up to a multiple of 8, plus
+ * 8 * (4 + 27 * ceil(W / 9)) bytes per item (the float64 partial row), n_partners * sum over the regions of ceil(n /
+ * 65536) items -- like hipdsp_region_stats it may not come between phase 1 and phase 2 of hipdsp_sosfilt_envelope.
+ * Determinism: no atomics.  The chunk and tile grids are anchored at the region's own start and sized by constants, the
+ * split of a tile among threads depends on max_lag alone, and tiles, segments and chunks are added in ascending order: a
+ * (region, partner) row and its info depend on those two rows' samples, on frames and on max_lag only -- not on which
+ * other regions or partners ride in the call, on their order, or on channels -- and the same call gives the same bytes
+ * twice.  Index arithmetic is 64-bit; rows start at any 4-byte address. */
+int hipdsp_region_xcorr(hipdsp_ctx *ctx, const float *x, int64_t x_pitch, int64_t channels, int64_t frames,
+                        const int64_t *host_regions, int64_t n_regions, const int *host_partners, int n_partners,
+                        int max_lag, float *out, int64_t out_pitch, double *info);
+
 /* The power envelope at the envelope rate: the first step of the reference's song detector, envelope()
  * (songdetector.py:57-69) -- the squares of a band-passed trace, a zero-phase low-pass of them, every step-th sample, the
  * clamp at zero and the root -- in one call that never writes anything at full rate.

@@ -271,6 +271,25 @@ for b in builds:
         logs[b['name']].append(f'{"hipdsp_common_reference, " + mode + ", one group of 64 channels":78s} {ms:8.3f} ms {8.0*S/ms/1e6:7.0f} GB/s')
         if b is builds[-1]:
             print(logs[b['name']][-1], flush=True)
+# ---- hipdsp_region_xcorr: the same ten 7 s events per channel of the filtered buffer against 8 partner channels over +-1 ms
+# (tools/region_xcorr_bench.py has all 63 partners, the envelope at +-50 ms, lag 0 alone and the measured float64 FMA rate)
+for b in builds:
+    h, ctx = b['h'], b['ctx']
+    if not hasattr(h.lib, 'hipdsp_region_xcorr'):
+        continue
+    n7 = min(int(7*rate), T//10)
+    table = np.array([(c, k*(T//10), k*(T//10) + n7) for c in range(C) for k in range(10)], dtype=np.int64)
+    for L in (96, 0):
+        rows, info = h.DeviceArray(ctx, (len(table), 8, 2*L + 1), np.float32), h.DeviceArray(ctx, (len(table), 8, 4), np.float64)
+        ms = min(timed(b, lambda: h.region_xcorr_into(ctx, b['buf']['df'], T, C, T, table, list(range(8)), L, rows, info), 1)
+                 for _ in range(rounds))
+        ctx.synchronize()
+        nbytes = 4.0*len(table)*8*(2*n7 + -(-n7//2048)*2*L)
+        logs[b['name']].append(f'{"hipdsp_region_xcorr, 10 events of 7 s per channel, 8 partners, max_lag " + str(L):78s} {ms:8.3f} ms {nbytes/ms/1e6:7.0f} GB/s')
+        if b is builds[-1]:
+            print(logs[b['name']][-1], flush=True)
+        rows.free()
+        info.free()
 prefix = os.environ.get('OUT_PREFIX')
 if prefix:
     for name, lines in logs.items():
