@@ -372,3 +372,35 @@ class CrossCorrelationAnalyzer(Analyzer):
         for k in range(len(src)):
             self.store(int(src[k]), float(delay[k]), float(corr[k]))
         return True
+
+
+class ContourAnalyzer(Analyzer):
+    """The frequency contour of the region on a spectrogram (TraceGraph.region_contours; contours.Contours has the
+    definitions): where the call starts, ends and peaks in frequency, its lowest and highest frequency, the extent
+    `drop_db` below the peak, power-weighted centroid, bandwidth and flatness, the region's frames and the share of them
+    with a peak above `min_power`.  One row per region and channel; NaN where no frame is above the floor."""
+
+    def __init__(self, graph, source_name='spectrogram', fmin=0.0, fmax=None, min_power=1e-20, drop_db=10.0):
+        super().__init__(graph, 'contour', source_name)
+        from .contours import FIELDS
+        from .hipdsp import drop_ratio
+        drop_ratio(drop_db)
+        self.fmin, self.fmax, self.min_power, self.drop_db = fmin, fmax, float(min_power), float(drop_db)
+        for name in FIELDS:
+            if name in ('n_frames', 'voiced', 'flatness'):
+                self.make_column(name.replace('_', ' '), '', '%.0f' if name == 'n_frames' else '%.3f')
+            else:
+                self.make_column(name.replace('_', ' '), 'Hz', '%.1f')
+
+    def _store(self, rows):
+        contours = self.graph.region_contours(rows, self.source_name, self.fmin, self.fmax, self.min_power, self.drop_db)
+        for i in range(len(contours)):
+            self.store(*contours.row(i))
+
+    def analyze(self, t0, t1, channel, traces):
+        self._store([(channel, t0, t1)])
+
+    def analyze_many(self, regions, channels):
+        # one device call for all regions and channels, the rows in region-major order
+        self._store([(c, t0, t1) for t0, t1 in regions for c in channels])
+        return True

@@ -78,8 +78,8 @@ class BufferedBandPower(BufferedData):
 
     def process(self, source, dest, nbefore):
         """dest[t, c] = scale * sum(source[nbefore + t, c, k0:k1]), in dB with `log`; the spectrogram's zero tail
-        frames give 0 (-inf)."""
-        from . import hipdsp
+        frames give 0 (-inf).  The steps are shared with the traces derived from this class, which supply
+        _launch() and _host_values()."""
         n = len(dest)
         self._check_lengths(source, dest, nbefore)
         call = self._take_call(source, dest)
@@ -89,12 +89,20 @@ class BufferedBandPower(BufferedData):
         if on_mirror is not None:
             spec, spitch = on_mirror
             ddst, dpitch, is_mirror = self._device_dest(dest, call)
-            hipdsp.band_power(self.ctx, spec, spitch, self.channels, n, self.source._inner(), [(self.k0, self.k1)],
-                              self.scale, ddst, db=self.log, min_power=self.min_power, out_pitch=dpitch)
+            self._launch(spec, spitch, n, ddst, dpitch)
             self._finish_dest(dest, ddst, dpitch, is_mirror, call)
             return
         # no mirror to read (a plain host array, a host-only graph): numpy in float64
-        slab = np.asarray(source[nbefore:nbefore + n], dtype=np.float64)
-        power = self.scale*np.sum(slab[:, :, self.k0:self.k1], axis=2)
-        dest[...] = decibel(power, 1.0, self.min_power) if self.log else power
+        dest[...] = self._host_values(np.asarray(source[nbefore:nbefore + n], dtype=np.float64))
         self._host_wrote(call)
+
+    def _launch(self, spec, spitch, n, ddst, dpitch):
+        """One launch over `n` frames of the spectrogram's mirror at `spec` into the planar rows at `ddst`."""
+        from . import hipdsp
+        hipdsp.band_power(self.ctx, spec, spitch, self.channels, n, self.source._inner(), [(self.k0, self.k1)],
+                          self.scale, ddst, db=self.log, min_power=self.min_power, out_pitch=dpitch)
+
+    def _host_values(self, slab):
+        """The same values of a (frames, channels, nfreq) float64 host slab."""
+        power = self.scale*np.sum(slab[:, :, self.k0:self.k1], axis=2)
+        return decibel(power, 1.0, self.min_power) if self.log else power

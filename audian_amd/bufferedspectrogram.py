@@ -266,6 +266,37 @@ class BufferedSpectrogram(BufferedData):
         power = np.stack([self.fresolution*np.sum(slab[:, :, k0:k1], axis=2).T for k0, k1 in bins])
         return (decibel(power, 1.0, min_power) if log else power).astype(np.float32)
 
+    def spectral_features(self, i0, i1, fmin=0.0, fmax=None, features=('peak_freq', 'peak_power'), min_power=1e-20,
+                          drop_db=10.0):
+        """Spectral contour features of the bins with frequencies in [fmin, fmax] (Hz, fmax None = Nyquist; the bins of
+        band_bins()) for frames [i0, i1) (absolute frame indices inside the current buffer): ``{name: (i1 - i0,
+        channels) float32}`` for every name of `features` (hipdsp.SPECTRAL_FEATURES), the frequencies in Hz, NaN where
+        the band's peak power is not above `min_power`.  With a valid device mirror ONE launch serves all requested
+        features (hipdsp_spectral_features) and only the result crosses PCIe; else numpy in float64."""
+        from . import hipdsp
+        from .bufferedspectralfeature import host_spectral_features
+        F = self.nfft//2 + 1
+        a, b = int(i0) - self.offset, int(i1) - self.offset
+        n = len(self._hostbuf)
+        if a < 0 or b > n or b < a:
+            raise IndexError('range outside the loaded buffer')
+        mask = hipdsp.feature_mask(features)
+        names = hipdsp.feature_names(mask)
+        hipdsp.drop_ratio(drop_db)
+        k0, k1 = band_bins(fmin, fmax, self.fresolution, F)
+        m = b - a
+        if m == 0:
+            return {name: np.zeros((0, self.channels), dtype=np.float32) for name in names}
+        if self._mirror_valid(a, b):
+            out = hipdsp.DeviceArray(self.ctx, (len(names), self.channels, m), np.float32)
+            hipdsp.spectral_features(self.ctx, self._dev.view(a*F, (1,)), self._pitch(), self.channels, m, F, k0, k1,
+                                     mask, self.fresolution, out, min_power=min_power, drop_db=drop_db)
+            rows = out.to_host().transpose(0, 2, 1)
+            out.free()
+        else:
+            rows = host_spectral_features(self.buffer[a:b], k0, k1, mask, self.fresolution, min_power, drop_db)
+        return {name: np.ascontiguousarray(rows[j]) for j, name in enumerate(names)}
+
     def estimate_noiselevels(self, channel):
         """Colour range for the spectrogram image (bufferedspectrogram.py:109-126): 95th
         percentile of the dB values in the top 1/16 of the band, and the maximum dB.  With a

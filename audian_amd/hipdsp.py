@@ -581,6 +581,56 @@ def band_power(ctx, spec, spec_pitch, channels, frames, nfreq, bands, scale, out
                                 int(out_pitch), int(out_band_pitch)))
 
 
+# the bits of hipdsp_spectral_features' mask, in bit order (HIPDSP_FEATURE_ in include/hip_dsp.h)
+SPECTRAL_FEATURES = ('peak_bin_freq', 'peak_freq', 'peak_power', 'centroid', 'bandwidth', 'flatness', 'freq_low',
+                     'freq_high')
+
+
+def feature_mask(features):
+    """The mask of a tuple of names of SPECTRAL_FEATURES (or of one name; a mask is checked and passed through);
+    ValueError for an unknown name, an empty selection or bits above 7."""
+    if isinstance(features, str):
+        features = (features,)
+    if isinstance(features, (int, np.integer)):
+        mask = int(features)
+    else:
+        mask = 0
+        for name in features:
+            if name not in SPECTRAL_FEATURES:
+                raise ValueError(f'unknown spectral feature {name!r}: one of {", ".join(SPECTRAL_FEATURES)}')
+            mask |= 1 << SPECTRAL_FEATURES.index(name)
+    if mask <= 0 or mask >= 1 << len(SPECTRAL_FEATURES):
+        raise ValueError(f'spectral features: mask {mask:#x} selects nothing or bits above {len(SPECTRAL_FEATURES) - 1}')
+    return mask
+
+
+def feature_names(mask):
+    """The names of a mask's features in the order their rows are stored (ascending bit order)."""
+    return tuple(name for b, name in enumerate(SPECTRAL_FEATURES) if feature_mask(mask) >> b & 1)
+
+
+def drop_ratio(drop_db):
+    """10^(-drop_db/10), the fraction of the peak power that bounds freq_low / freq_high; ValueError for drop_db < 0."""
+    drop_db = float(drop_db)
+    if not drop_db >= 0:
+        raise ValueError(f'drop_db must be >= 0, got {drop_db}')
+    return 10.0**(-drop_db/10.0)
+
+
+def spectral_features(ctx, spec, spec_pitch, channels, frames, nfreq, k0, k1, features, scale, out, min_power=0.0,
+                      drop_db=10.0, out_pitch=0, out_feature_pitch=0):
+    """out[j, c, t] = the j-th of the requested `features` (names of SPECTRAL_FEATURES or a mask; rows in bit order) of
+    the bins [k0, k1) of spec[c, t], float32 (hipdsp_spectral_features): peak, centroid, bandwidth, flatness and extent
+    of the band in one launch; NaN where the peak power is not finite or not above min_power."""
+    mask, ratio = feature_mask(features), drop_ratio(drop_db)
+    if not ratio > 0:
+        raise ValueError(f'drop_db {drop_db} is too large: 10^(-drop_db/10) underflows')
+    _count('spectral_features')
+    check(lib.hipdsp_spectral_features(ctx.handle, _p(spec), int(spec_pitch), int(channels), int(frames), int(nfreq),
+                                       int(k0), int(k1), mask, float(scale), float(min_power), ratio, _p(out),
+                                       int(out_pitch), int(out_feature_pitch)))
+
+
 def fir_bank(ctx, plan, x, x_pitch, channels, frames, first, step, n_out, out, rectify=False, out_pitch=0,
              out_kernel_pitch=0):
     """out[k, c, i] = sum_j taps[k, j] * x[c, first + i*step + (L-1)//2 - j] for every kernel of `plan`, x zero outside

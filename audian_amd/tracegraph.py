@@ -245,6 +245,30 @@ class TraceGraph(object):
                 self._event_frames(trace, (a + 0.5)/trace.rate, (b - 0.5)/trace.rate)       # as Events.regions
         return trace.region_xcorr(table, channels, max_lag)
 
+    def region_contours(self, rows, spec_name='spectrogram', fmin=0.0, fmax=None, min_power=1e-20, drop_db=10.0):
+        """The frequency contours (contours.Contours) of the (channel, t_on, t_off) `rows` in seconds on the spectrogram
+        `spec_name`, inside the band [fmin, fmax] Hz: every row owns the frames whose centre lies in it.  The buffers are
+        moved as in detect_events so that the spectrogram holds all rows, then ONE spectral_features call over the frames
+        they span (BufferedSpectrogram.spectral_features: on its device mirror when it has one) brings seven floats per
+        frame and channel, and the per-event reduction runs on the host."""
+        from .contours import CONTOUR_FEATURES, Contours, frame_table
+        spec = self[spec_name]
+        rate = spec.source.rate
+        table = frame_table(rows, rate, spec.nfft, spec.hop, spec.frames)
+        a = int(table[:, 1].min()) if len(table) else spec.offset
+        b = max(a, int(table[:, 2].max())) if len(table) else a
+        if b > a and (a < spec.offset or b > spec.offset + len(spec._buf())):
+            self._event_frames(spec, (a + 0.5)/spec.rate, (b - 0.5)/spec.rate)      # as Events.regions
+        feats = spec.spectral_features(a, b, fmin, fmax, CONTOUR_FEATURES, min_power, drop_db)
+        return Contours(table, a, feats, 0.5*spec.nfft/rate, spec.hop/rate, spec.name)
+
+    def event_contours(self, events, spec_name='spectrogram', fmin=0.0, fmax=None, min_power=1e-20, drop_db=10.0):
+        """region_contours of every event [onset, offset) / events.rate, channel by channel in the events' order:
+        start, end, minimum, maximum and peak frequency of every call, its extent, centroid, bandwidth and flatness."""
+        rows = [(c, a/events.rate, b/events.rate) for c in range(events.channels)
+                for a, b in events.frames(c).tolist()]
+        return self.region_contours(rows, spec_name, fmin, fmax, min_power, drop_db)
+
     def attribute_events(self, events, trace_name=None, max_delay=0.001, channels=None, min_r=0.5, min_ratio=1.0):
         """event_cross_correlation followed by the attribution rule (xcorr.attribute_events, whose two thresholds are
         not calibrated on recordings): returns (own, sources, delays) -- the Events that are their own source, and per

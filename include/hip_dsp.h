@@ -583,6 +583,54 @@ int hipdsp_band_power(hipdsp_ctx *ctx, const float *spec, int64_t spec_pitch, in
                       int n_bands, double scale, int db, double ref_power, double min_power,
                       float *out, int64_t out_pitch, int64_t out_band_pitch);
 
+/* Spectral contour features: where the power inside a band of bins sits in frequency, per frame and channel -- what a
+ * user reads off a spectrogram (peak frequency, its sweep inside a call, tonal or noisy) without the slab leaving the
+ * device.  spec, spec_pitch and the alignment-free rows are those of hipdsp_band_power; the band is the bins [k0, k1),
+ * 0 <= k0 <= k1 <= nfreq.  `features` is a mask of the HIPDSP_FEATURE_ bits below; the rows of the requested features
+ * are stored in ascending bit order,
+ *   out[j*out_feature_pitch + c*out_pitch + t],   j = number of set bits below the feature's own
+ * (out_pitch 0 = frames, out_feature_pitch 0 = channels*out_pitch).  scale is the bin width in Hz (1.0: bins).
+ * With P[k] the float32 bin, n = k1 - k0, sums over the band, and all arithmetic in float64 (no fused multiply-add),
+ * every stored value rounded to float32 once:
+ *   bit 0 PEAK_BIN_FREQ  scale*kp, kp = np.argmax(P[k0:k1]) + k0: the first of equal maxima, the first NaN if any
+ *   bit 1 PEAK_FREQ      scale*(kp + d), d = 0.5*(a - c)/((a - 2b) + c) with a, b, c = ln P[kp-1], ln P[kp], ln P[kp+1]
+ *                        if kp-1 >= k0, kp+1 < k1, both neighbours > 0 and (a - 2b) + c < 0; else d = 0 (a peak at the
+ *                        band's edge, a zero neighbour, a plateau of three equal bins)
+ *   bit 2 PEAK_POWER     P[kp] exactly
+ *   bit 3 CENTROID       scale*(kp + M1/S), S = sum P[k], M1 = sum (k - kp) P[k]
+ *   bit 4 BANDWIDTH      scale*sqrt(max(M2/S - (M1/S)^2, 0)), M2 = sum (k - kp)^2 P[k]: the moments are taken about
+ *                        the peak, which keeps the subtraction conditioned for a narrow line anywhere in the band
+ *   bit 5 FLATNESS       exp(sum(ln P[k])/n) / (S/n), the Wiener entropy: 1 for a flat band, 0 once a bin is 0
+ *   bit 6 FREQ_LOW       scale*klo, klo the first k with (double)P[k] >= drop_ratio*(double)P[kp]
+ *   bit 7 FREQ_HIGH      scale*khi, khi the last such k;  0 < drop_ratio <= 1 (10^(-dB/10), from the host)
+ * Masking: if P[kp] is not finite or not > min_power -- NaN or +inf in the band, an empty band, a silent frame, the
+ * spectrogram's zero tail frames with min_power >= 0 -- every feature except PEAK_POWER is NaN; PEAK_POWER is P[kp]
+ * as it is, NaN for an empty band.  The input contract is non-negative bins, as every spectrogram entry point writes
+ * them.
+ * HIPDSP_ERR_INVALID: NULL ctx, NULL spec or out with work to do, a negative size or pitch, a band outside [0, nfreq],
+ * features == 0 or bits above 7, drop_ratio outside (0, 1], a pitch too small for the sizes.  frames == 0 or
+ * channels == 0: nothing is written.  Limits: at most 65535 channels, nfreq <= 2^26 (all of nfft 8 ... 2^19 and
+ * beyond), 2^24 - 1 frames per call (2^28 - 1 with nfreq <= 256).
+ * Promises: no atomics; no context scratch and no upload -- all arguments travel by value, the call is one kernel node
+ * inside hipdsp_graph_begin/end; the same call gives the same bits twice; what a frame stores depends on that frame's
+ * band alone, not on the other channels or frames of the call, the pitches or which other features are requested (the
+ * mapping is chosen by nfreq alone, a thread's share of a row by the absolute bin index); only bins inside the band
+ * are read, nothing outside the requested rows is written; index arithmetic on the slab is 64-bit.  A band of up to
+ * 8448 bins is read from memory once (it waits in LDS between the two passes), a wider one twice.  log() is
+ * evaluated once per bin only with FLATNESS and three times per row with PEAK_FREQ. */
+#define HIPDSP_FEATURE_PEAK_BIN_FREQ 1u
+#define HIPDSP_FEATURE_PEAK_FREQ 2u
+#define HIPDSP_FEATURE_PEAK_POWER 4u
+#define HIPDSP_FEATURE_CENTROID 8u
+#define HIPDSP_FEATURE_BANDWIDTH 16u
+#define HIPDSP_FEATURE_FLATNESS 32u
+#define HIPDSP_FEATURE_FREQ_LOW 64u
+#define HIPDSP_FEATURE_FREQ_HIGH 128u
+int hipdsp_spectral_features(hipdsp_ctx *ctx, const float *spec, int64_t spec_pitch, int64_t channels,
+                             int64_t frames, int64_t nfreq, int64_t k0, int64_t k1, unsigned features,
+                             double scale, double min_power, double drop_ratio, float *out, int64_t out_pitch,
+                             int64_t out_feature_pitch);
+
 /* ---- FIR kernel bank ("feature expansion (kernel filter)") ----------------- */
 
 /* A plan holds, in device memory, the taps and thresholds of up to 16 FIR kernels of one common length, as

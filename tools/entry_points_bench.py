@@ -138,6 +138,20 @@ for b in builds:
         logs[b['name']].append(f'{"hipdsp_band_power over the PSD 2048/1024, " + name:78s} {ms:8.3f} ms {nbytes/ms/1e6:7.0f} GB/s')
         if b is builds[-1]:
             print(logs[b['name']][-1], flush=True)
+# ---- hipdsp_spectral_features over the same PSD slab (the loop above has just written it; tools/spectral_features_bench.py has
+# the 1/8 band and hipdsp_band_power next to every line): the peak alone, and all eight features
+for b in builds:
+    h, ctx = b['h'], b['ctx']
+    if not hasattr(h.lib, 'hipdsp_spectral_features'):
+        continue
+    ds, out = b['buf']['ds'], b['buf']['db']            # (nothing below reads the dB image's buffer)
+    for name, mask in (('peak bin, peak and peak power', 0x07), ('all eight features', 0xFF)):
+        nbytes = 4.0*C*nd*(F + bin(mask).count('1'))
+        ms = min(timed(b, lambda: h.spectral_features(ctx, ds, 0, C, nd, F, 0, F, mask, rate/nfft, out), 5) for _ in range(rounds))
+        ctx.synchronize()
+        logs[b['name']].append(f'{"hipdsp_spectral_features over the PSD 2048/1024, full band, " + name:78s} {ms:8.3f} ms {nbytes/ms/1e6:7.0f} GB/s')
+        if b is builds[-1]:
+            print(logs[b['name']][-1], flush=True)
 # ---- hipdsp_fir_bank: 16 kernels of 257 taps over the envelope, one frame per millisecond (tools/fir_bank_bench.py has the
 # other kernel lengths and steps)
 for b in builds:
