@@ -361,16 +361,7 @@ int hipdsp_chain_forward(hipdsp_ctx *ctx, const hipdsp_sosplan *fplan, const hip
     // frames inside the trace, as in hipdsp_spectrogram (bufferedspectrogram.py:46-49); the spectrogram may be
     // handed fewer samples than the filter produces (spec_frames: BufferedData.load_buffer's one frame "after")
     const long long sframes = spec_frames > 0 ? spec_frames : frames - spec_first;
-    long long nsource = (frames_out - 1) * (long long)hop + nfft;
-    if (nsource > sframes) nsource = sframes;
-    long long n_valid = 0;
-    if (frames_out > 0 && nsource >= nfft) n_valid = (nsource - (nfft - hop)) / hop;
-    if (n_valid > frames_out) n_valid = frames_out;
-    double wss = 0.0;
-    for (int i = 0; i < nfft; i++) {
-        const double w = 0.5 - 0.5 * cos(2.0 * M_PI * (double)i / (double)nfft);
-        wss += w * w;
-    }
+    const long long n_valid = hd_frames_valid(frames_out, sframes, nfft, hop);
     ChainArgs a;
     memset(&a, 0, sizeof(a));
     int rc = hd_fft_tables(ctx, nfft, &a.tables);
@@ -380,19 +371,18 @@ int hipdsp_chain_forward(hipdsp_ctx *ctx, const hipdsp_sosplan *fplan, const hip
     const GridShift gs = hd_grid_shift(spec_first, env_first, hop, edge, SE > 0);
     HD_REQUIRE(gs.lead < TILE, "grid shift %lld", gs.lead);
     const long long T = frames + gs.lead;
-    const long long n_tiles = (T + edge + TILE - 1) / TILE;
-    const long long ckpt_pitch = (n_tiles + 1) * 2 * SE;           // the layout the backward sweep expects
+    const TileStates ts = hd_tile_states(T, edge, SE);
     void *work = nullptr;
     if (SE > 0) {
-        rc = hipdsp_scratch(ctx, sizeof(double) * (size_t)ckpt_pitch * (size_t)channels, &work);
+        rc = hipdsp_scratch(ctx, ts.bytes(channels), &work);
         if (rc != HIPDSP_OK) return rc;
     }
     a.c.in = x - gs.lead; a.c.yf = yf - gs.lead; a.c.ckpt = (double *)work;
-    a.c.in_pitch = x_pitch; a.c.yf_pitch = yf_pitch; a.c.ckpt_pitch = ckpt_pitch;
+    a.c.in_pitch = x_pitch; a.c.yf_pitch = yf_pitch; a.c.ckpt_pitch = ts.ckpt_pitch;
     a.c.T = T; a.c.edge = edge; a.c.rectify = rectify; a.c.gain = rectify ? gain : 1.0;
     a.c.lead = gs.lead; a.c.env0 = gs.env0; a.frame_off = gs.frame_off;
     a.psd = psd; a.db = db_out; a.psd_pitch = psd_pitch; a.n_valid = n_valid;
-    a.scale = (float)(1.0 / (fs * wss));
+    a.scale = (float)(1.0 / (fs * hd_hann_sumsq(nfft)));
     a.scale_half = 0.5f * a.scale; a.scale_twice = 2.f * a.scale;
     a.warm_total = fplan->host->warm;              // the envelope's states are handed over exactly (env_fix_kernel)
     a.debug = ctx->chain_debug;
@@ -446,15 +436,12 @@ int hipdsp_chain_forward(hipdsp_ctx *ctx, const hipdsp_sosplan *fplan, const hip
     if (stamp) return hd_launch_status("chain_fwd_kernel");
     rc = hd_launch_status("chain_fwd_kernel");
     if (rc != HIPDSP_OK) return rc;
-    FloodArgs fl;
-    memset(&fl, 0, sizeof(fl));
-    fl.flags = a.c.flags; fl.n_seg = a.c.n_seg; fl.seg_len = a.c.seg_len;
-    fl.y = yf; fl.y_pitch = yf_pitch; fl.T = T; fl.skip = gs.lead;       // (sample p' of the sweep is yf[p' - lead])
+    FloodArgs fl = hd_flood_args(a.c.flags, a.c.n_seg, a.c.seg_len, yf, yf_pitch, T, gs.lead);   // (sample p' is yf[p' - lead])
     fl.psd = psd; fl.db = db_out; fl.psd_pitch = psd_pitch; fl.n_valid = n_valid;
     fl.F = (int)F; fl.nfft = nfft; fl.hop = hop; fl.frame_off = gs.frame_off;
     rc = SE == 0 ? launch_flood(ctx, fl, channels)
-                 : hd_launch_env_fix(ctx, eplan->dev, SE, (double *)work, ckpt_pitch, channels, a.c.n_seg, a.c.seg_len, n_tiles, &fl,
-                                     (int)((gs.env0 - gs.env0 % TILE) / a.c.seg_len));
+                 : hd_launch_env_fix(ctx, eplan->dev, SE, (double *)work, ts.ckpt_pitch, channels, a.c.n_seg, a.c.seg_len,
+                                     ts.n_tiles, &fl, (int)((gs.env0 - gs.env0 % TILE) / a.c.seg_len));
     if (rc != HIPDSP_OK) return rc;
     // Only a sweep whose every launch went out has parked tile states: what a backward sweep (phase 2) must agree with.
     // (hipdsp_scratch() above forgot the sweep before; a return on the way leaves the context without one.)
@@ -494,22 +481,12 @@ int hipdsp_chain_backward(hipdsp_ctx *ctx, const hipdsp_sosplan *eplan, const fl
     const long long F = nfft / 2 + 1;
     if (psd_pitch == 0) psd_pitch = frames_out * F;
     HD_REQUIRE(psd_pitch >= frames_out * F, "psd_pitch smaller than one channel");
-    long long nsource = (frames_out - 1) * (long long)hop + nfft;
-    if (nsource > frames) nsource = frames;
-    long long n_valid = 0;
-    if (frames_out > 0 && nsource >= nfft) n_valid = (nsource - (nfft - hop)) / hop;
-    if (n_valid > frames_out) n_valid = frames_out;
-    double wss = 0.0;
-    for (int i = 0; i < nfft; i++) {
-        const double w = 0.5 - 0.5 * cos(2.0 * M_PI * (double)i / (double)nfft);
-        wss += w * w;
-    }
+    const long long n_valid = hd_frames_valid(frames_out, frames, nfft, hop);
     ChainBwdArgs a;
     memset(&a, 0, sizeof(a));
     int rc = hd_fft_tables(ctx, nfft, &a.tables);
     if (rc != HIPDSP_OK) return rc;
-    const long long n_tiles = (frames + edge + TILE - 1) / TILE;
-    const long long ckpt_pitch = (n_tiles + 1) * 2 * SE;           // where the forward sweep parked the tile states
+    const TileStates ts = hd_tile_states(frames, edge, SE);         // where the forward sweep parked the tile states
     void *work = nullptr;
     // the tile states in the scratch belong to the grid of the forward sweep that left them: this sweep walks the
     // unshifted grid only (after hipdsp_chain_forward with spec_first / env_first > 0 the states sit
@@ -523,20 +500,20 @@ int hipdsp_chain_backward(hipdsp_ctx *ctx, const hipdsp_sosplan *eplan, const fl
                          (long long)channels, (long long)frames, SE);
         return HIPDSP_ERR_INVALID;
     }
-    rc = hd_scratch_parked(ctx, sizeof(double) * (size_t)ckpt_pitch * (size_t)channels, &work);
+    rc = hd_scratch_parked(ctx, ts.bytes(channels), &work);
     if (rc != HIPDSP_OK) return rc;
     a.b.in = yf; a.b.in_pitch = yf_pitch;
     a.b.out = env; a.b.out_pitch = env_pitch;
-    a.b.ckpt = (const double *)work; a.b.ckpt_pitch = ckpt_pitch;
-    a.b.T = frames; a.b.skip = 0; a.b.n_tiles = n_tiles; a.b.edge = edge;
+    a.b.ckpt = (const double *)work; a.b.ckpt_pitch = ts.ckpt_pitch;
+    a.b.T = frames; a.b.skip = 0; a.b.n_tiles = ts.n_tiles; a.b.edge = edge;
     a.b.rectify = rectify; a.b.clamp = clamp; a.b.gain = rectify ? gain : 1.0;
     constexpr int P = 8;
     long long seg_len = 0;
-    plan_segments_chain(ctx, n_tiles * TILE, channels, eplan->host->warm, &seg_len, &a.b.n_seg);
+    plan_segments_chain(ctx, ts.n_tiles * TILE, channels, eplan->host->warm, &seg_len, &a.b.n_seg);
     a.b.seg_tiles = seg_len / TILE;
     a.b.warm_tiles = eplan->host->warm / TILE;
     a.psd = psd; a.psd_pitch = psd_pitch; a.n_valid = n_valid;
-    a.scale = (float)(1.0 / (fs * wss));
+    a.scale = (float)(1.0 / (fs * hd_hann_sumsq(nfft)));
     a.units = channels * a.b.n_seg;
     a.debug = ctx->chain_debug;
     a.fault = ctx->fault_dev;
@@ -549,7 +526,7 @@ int hipdsp_chain_backward(hipdsp_ctx *ctx, const hipdsp_sosplan *eplan, const fl
     if (rc != HIPDSP_OK) return rc;
     // (its paired waves cannot leave early like env_bwd_kernel's: the NaN channels are overwritten afterwards)
     hipLaunchKernelGGL(env_nan_fill_kernel, dim3(64, (unsigned)channels), dim3(256), 0, ctx->stream, (const double *)work,
-                       ckpt_pitch, n_tiles, 2 * SE, env, (long long)env_pitch, (long long)frames);
+                       ts.ckpt_pitch, ts.n_tiles, 2 * SE, env, (long long)env_pitch, (long long)frames);
     return hd_launch_status("env_nan_fill_kernel");
 }
 
@@ -560,7 +537,7 @@ int hipdsp_chain_backward_plan(hipdsp_ctx *ctx, const hipdsp_sosplan *eplan, int
     HD_REQUIRE(first_border != nullptr && segment_frames != nullptr && n_segments != nullptr, "NULL output");
     HD_REQUIRE(channels >= 1 && frames >= 1, "bad size");
     HD_REQUIRE(eplan->host->n_sections > 0, "plan has no coefficients");
-    const long long n_tiles = (frames + eplan->host->edge + TILE - 1) / TILE;
+    const long long n_tiles = hd_tile_states(frames, eplan->host->edge, eplan->host->n_sections).n_tiles;
     long long len = 0;
     int n = 0;
     plan_segments_chain(ctx, n_tiles * TILE, channels, eplan->host->warm, &len, &n);

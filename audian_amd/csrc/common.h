@@ -114,10 +114,29 @@ static inline bool hd_planar_overlap(const float *a, long long a_pitch, long lon
 #define HD_NO_OVERLAP(a, ap, af, b, bp, bf, channels, what)                                             \
     HD_REQUIRE(!hd_planar_overlap((a), (ap), (af), (b), (bp), (bf), (channels)), what " must not overlap")
 
+// is the context's stream inside a stream capture?  (the NULL stream cannot be)
+static inline bool hd_capturing(const hipdsp_ctx *ctx)
+{
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (ctx->stream) (void)hipStreamIsCapturing(ctx->stream, &st);
+    return st != hipStreamCaptureStatusNone;
+}
+
 int hipdsp_scratch(hipdsp_ctx *ctx, size_t bytes, void **out);
 // the scratch as a forward sweep left it (tile states of the envelope): for the backward sweeps; HIPDSP_ERR_INVALID when
 // anything has asked for the scratch since (hipdsp_scratch() forgets the sweep's note)
 int hd_scratch_parked(hipdsp_ctx *ctx, size_t bytes, void **out);
-// tw2 | tw3 | twn | window of the three-stage PSD kernel, device memory (spectrogram.hip): served for nfft 2048
-// (radix 16 x 16 x 4), 1024 (8 x 8 x 8), 512 (8 x 8 x 4) and 256 (8 x 4 x 4) -- the sizes chain_fwd_kernel is built for
+// ---- spec_host.hip: the host-side rules the spectrogram and the fused sweeps share (no device code) ----
+// Frames that lie inside a trace of `avail` samples: the number of k in [0, frames_out) with k * hop + nfft <= avail
+// (bufferedspectrogram.py:46-49 and scipy's _spectral_helper segment count); the frames behind them are the zero tail.
+long long hd_frames_valid(long long frames_out, long long avail, int nfft, int hop);
+// Sum of squares of the periodic Hann window, in float64: the PSD scale is 1 / (fs * this).  The fused sweeps and
+// hipdsp_spectrogram must agree on it to the bit (the facade swaps one for the other).
+double hd_hann_sumsq(int nfft);
+// The twiddle and window tables of one nfft in device memory, built in float64 on first use and kept in the context:
+// R3 > 0: tw2 | tw3 | twn | window of the three-stage kernels (radices R1 x R2 x R3; hipdsp_ctx::fft_tables),
+// R3 == 0: tw2 | twn | window of the two-stage kernels (R1 x R2; hipdsp_ctx::fft_tables2).
+int hd_fft_table_set(hipdsp_ctx *ctx, int nfft, int R1, int R2, int R3, const float **dev);
+// the three-stage set of the sizes chain_fwd_kernel is built for: nfft 2048 (radix 16 x 16 x 4), 1024 (8 x 8 x 8),
+// 512 (8 x 8 x 4) and 256 (8 x 4 x 4)
 int hd_fft_tables(hipdsp_ctx *ctx, int nfft, const float **dev);

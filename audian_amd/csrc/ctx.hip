@@ -280,14 +280,13 @@ int hipdsp_malloc(hipdsp_ctx *ctx, size_t bytes, void **dptr)
     HD_CHECK_HIP(hipSetDevice(ctx->device));
     hd_pool *p = ctx->pool;
     const size_t want = (bytes + 511) & ~(size_t)511;
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    if (ctx->stream) (void)hipStreamIsCapturing(ctx->stream, &capturing);
+    const bool capturing = hd_capturing(ctx);
     auto it = p->cached.lower_bound(want);
     // A block freed on ANOTHER stream needs an order between the two: an event wait -- which must not be issued into
     // a stream capture (the event was recorded outside it) and does not exist for a block that was freed DURING a
     // capture (no event could be recorded then).  Such candidates are passed over.
     while (it != p->cached.end() && it->first <= want + want / 4 + 4096 && it->second.stream != ctx->stream &&
-           (it->second.freed == nullptr || capturing != hipStreamCaptureStatusNone))
+           (it->second.freed == nullptr || capturing))
         ++it;
     if (it != p->cached.end() && it->first <= want + want / 4 + 4096) {
         const hd_block b = it->second;
@@ -329,11 +328,9 @@ int hipdsp_malloc_probed(hipdsp_ctx *ctx, size_t bytes, int tries, void **dptr)
 {
     HD_REQUIRE(ctx != nullptr && dptr != nullptr, "NULL argument");
     *dptr = nullptr;
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    if (ctx->stream) (void)hipStreamIsCapturing(ctx->stream, &capturing);
     if (tries > 8) tries = 8;
     // small blocks (the differences are a few per cent of a stream over the block) and captures: a plain allocation
-    if (tries <= 1 || bytes < ((size_t)64 << 20) || capturing != hipStreamCaptureStatusNone) return hipdsp_malloc(ctx, bytes, dptr);
+    if (tries <= 1 || bytes < ((size_t)64 << 20) || hd_capturing(ctx)) return hipdsp_malloc(ctx, bytes, dptr);
     void *cand[8];
     float ms[8];
     int n = 0;
@@ -387,9 +384,7 @@ int hipdsp_free(hipdsp_ctx *ctx, void *dptr)
     p->live.erase(it);
     if (size <= p->max_block && p->cached_bytes + size <= p->limit) {
         hd_block b{dptr, ctx->stream, nullptr};
-        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-        if (ctx->stream) (void)hipStreamIsCapturing(ctx->stream, &st);
-        if (st == hipStreamCaptureStatusNone) {
+        if (!hd_capturing(ctx)) {
             hipError_t e = hipSuccess;
             if (!p->spare_events.empty()) {
                 b.freed = p->spare_events.back();
@@ -650,9 +645,7 @@ int hd_device_fault(hipdsp_ctx *ctx)
 static int hd_fill_block(hipdsp_ctx *ctx, void *block, size_t bytes)
 {
     if (block == nullptr || bytes == 0) return HIPDSP_OK;
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (ctx->stream) (void)hipStreamIsCapturing(ctx->stream, &st);
-    if (st != hipStreamCaptureStatusNone) return HIPDSP_OK;
+    if (hd_capturing(ctx)) return HIPDSP_OK;
     HD_CHECK_HIP(hipMemsetAsync(block, ctx->scratch_fill - 1, bytes, ctx->stream));
     return HIPDSP_OK;
 }
@@ -660,9 +653,7 @@ static int hd_fill_block(hipdsp_ctx *ctx, void *block, size_t bytes)
 int hd_seg_flags(hipdsp_ctx *ctx, size_t units, unsigned char **out)
 {
     if (units > ctx->seg_flags_cap) {
-        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-        if (ctx->stream) (void)hipStreamIsCapturing(ctx->stream, &st);
-        if (st != hipStreamCaptureStatusNone || ctx->graphs_alive > 0) {
+        if (hd_capturing(ctx) || ctx->graphs_alive > 0) {
             hipdsp_set_error("a sweep of %zu (channel, segment) units during a stream capture or next to captured graphs of "
                              "this context: run one of that size once before capturing", units);
             return HIPDSP_ERR_INVALID;
@@ -710,9 +701,7 @@ int hipdsp_scratch(hipdsp_ctx *ctx, size_t bytes, void **out)
     // which READ the parked states, take the pointer through hd_scratch_parked() instead.
     ctx->sweep_frames = -1;
     if (bytes > ctx->scratch_bytes) {
-        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-        if (ctx->stream) (void)hipStreamIsCapturing(ctx->stream, &st);
-        if (st != hipStreamCaptureStatusNone) {
+        if (hd_capturing(ctx)) {
             hipdsp_set_error("scratch of %zu bytes needed during stream capture; call "
                              "hipdsp_ctx_reserve() before capturing", bytes);
             return HIPDSP_ERR_INVALID;

@@ -279,9 +279,7 @@ int hipdsp_firplan_upload(hipdsp_ctx *ctx, hipdsp_firplan *plan)
                                 hipMemcpyHostToDevice, ctx->stream));
     plan->up_kernels = plan->n_kernels;
     plan->up_taps = plan->n_taps;
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (ctx->stream) (void)hipStreamIsCapturing(ctx->stream, &st);
-    if (st == hipStreamCaptureStatusNone) {
+    if (!hd_capturing(ctx)) {
         HD_CHECK_HIP(hipEventRecord(plan->uploaded, ctx->stream));
         plan->valid = true;
     }

@@ -391,9 +391,7 @@ extern "C" int hipdsp_power_envelope(hipdsp_ctx *ctx, const hipdsp_sosplan *plan
     HD_REQUIRE(y_pitch >= n_out, "y_pitch smaller than n_out");
     HD_REQUIRE(((uintptr_t)x & 3) == 0 && ((uintptr_t)y & 3) == 0, "misaligned pointer");
     HD_NO_OVERLAP(x, x_pitch, frames, y, y_pitch, n_out, channels, "x and y");
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (ctx->stream) (void)hipStreamIsCapturing(ctx->stream, &st);
-    HD_REQUIRE(st == hipStreamCaptureStatusNone, "hipdsp_power_envelope sizes its scratch per call: not during stream capture");
+    HD_REQUIRE(!hd_capturing(ctx), "hipdsp_power_envelope sizes its scratch per call: not during stream capture");
     const SosPlanDev &host = *plan->host;
     const int S = host.n_sections;
     if (S < 1 || S > 2) {

@@ -247,11 +247,7 @@ extern "C" int hipdsp_region_spectra(hipdsp_ctx *ctx, const float *x, int64_t x_
     const SpRegion *dtab = (const SpRegion *)work;
     double *part = (double *)((char *)work + tab_bytes);
     HD_TRY(hd_upload_table(ctx, work, tab.data(), tab_bytes));
-    double sw2 = 0.0;
-    for (int i = 0; i < nfft; i++) {
-        const double w = 0.5 - 0.5 * cos(2.0 * M_PI * (double)i / (double)nfft);
-        sw2 += w * w;
-    }
+    const double sw2 = hd_hann_sumsq(nfft);
     if (items > 0) {
         const size_t lds = sizeof(float2) * 3 * (size_t)(nfft / 2);
         if (lds > 48 * 1024)

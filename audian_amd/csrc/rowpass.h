@@ -261,9 +261,7 @@ static inline int hd_check_table(const char *who, hipdsp_ctx *ctx, const float *
         HD_REQUIRE(a >= 0 && a <= b && b <= frames, "region %lld: elements [%lld, %lld) not inside [0, %lld]", (long long)r,
                    (long long)a, (long long)b, (long long)frames);
     }
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (ctx->stream) (void)hipStreamIsCapturing(ctx->stream, &st);
-    if (st != hipStreamCaptureStatusNone) {
+    if (hd_capturing(ctx)) {
         hipdsp_set_error("%s reads its region table from host memory: not during stream capture", who);
         return HIPDSP_ERR_INVALID;
     }

@@ -920,11 +920,7 @@ int launch_scan(hipdsp_ctx *ctx, const SosPlanDev *dev, int S, SeqArgs a, long l
     }
     const int rc = hd_launch_status("sos_scan_kernel");
     if (rc != HIPDSP_OK || a.flags == nullptr) return rc;
-    FloodArgs fl;
-    memset(&fl, 0, sizeof(fl));
-    fl.flags = a.flags; fl.n_seg = a.n_seg; fl.seg_len = a.seg_len;
-    fl.y = a.out; fl.y_pitch = a.out_pitch; fl.T = a.N; fl.skip = a.skip;
-    return launch_flood(ctx, fl, channels);
+    return launch_flood(ctx, hd_flood_args(a.flags, a.n_seg, a.seg_len, a.out, a.out_pitch, a.N, a.skip), channels);
 }
 
 // Envelope by checkpoints: forward sweep (optionally with the band-pass in front), then the
@@ -942,17 +938,15 @@ int launch_env_ckpt(hipdsp_ctx *ctx, const SosPlanDev *fdev, const SosPlanDev *e
     if (yf) yf -= gs.lead;
     frames += gs.lead;
     skip += gs.env0;
-    const long long n_tiles = (frames + edge + TILE - 1) / TILE;
-    const long long ckpt_pitch = (n_tiles + 1) * 2 * SE;     // (+ 1: the state the channel ends with, FloodArgs)
+    const TileStates ts = hd_tile_states(frames, edge, SE);
     void *work = nullptr;
-    int rc = phase == 2 ? hd_scratch_parked(ctx, sizeof(double) * (size_t)ckpt_pitch * (size_t)channels, &work)
-                        : hipdsp_scratch(ctx, sizeof(double) * (size_t)ckpt_pitch * (size_t)channels, &work);
+    int rc = phase == 2 ? hd_scratch_parked(ctx, ts.bytes(channels), &work) : hipdsp_scratch(ctx, ts.bytes(channels), &work);
     if (rc != HIPDSP_OK) return rc;
     if (phase != 2) {
         CkptArgs fa;
         memset(&fa, 0, sizeof(fa));
         fa.in = x; fa.yf = yf; fa.ckpt = (double *)work;
-        fa.in_pitch = x_pitch; fa.yf_pitch = yf_pitch; fa.ckpt_pitch = ckpt_pitch;
+        fa.in_pitch = x_pitch; fa.yf_pitch = yf_pitch; fa.ckpt_pitch = ts.ckpt_pitch;
         fa.T = frames; fa.edge = edge; fa.rectify = rectify; fa.gain = rectify ? gain : 1.0;
         fa.lead = gs.lead; fa.env0 = gs.env0;
         // only the band-pass warms up; the envelope's states are handed over exactly (env_fix_kernel), which needs
@@ -989,11 +983,9 @@ int launch_env_ckpt(hipdsp_ctx *ctx, const SosPlanDev *fdev, const SosPlanDev *e
 #undef HD_CKPT
         rc = hd_launch_status("sos_ckpt_kernel");
         if (rc != HIPDSP_OK) return rc;
-        FloodArgs fl;
-        memset(&fl, 0, sizeof(fl));
-        fl.flags = fa.flags; fl.n_seg = fa.n_seg; fl.seg_len = fa.seg_len;
-        fl.y = yf ? yf + gs.lead : nullptr; fl.y_pitch = yf_pitch; fl.T = frames; fl.skip = gs.lead;
-        rc = launch_env_fix(ctx, edev, SE, (double *)work, ckpt_pitch, channels, fa.n_seg, fa.seg_len, n_tiles, &fl,
+        const FloodArgs fl =
+            hd_flood_args(fa.flags, fa.n_seg, fa.seg_len, yf ? yf + gs.lead : nullptr, yf_pitch, frames, gs.lead);
+        rc = launch_env_fix(ctx, edev, SE, (double *)work, ts.ckpt_pitch, channels, fa.n_seg, fa.seg_len, ts.n_tiles, &fl,
                             (int)((gs.env0 - gs.env0 % TILE) / fa.seg_len));
         if (rc != HIPDSP_OK) return rc;
         // every launch of the forward sweep went out: only now are its tile states parked (hipdsp_scratch() forgot the
@@ -1007,15 +999,15 @@ int launch_env_ckpt(hipdsp_ctx *ctx, const SosPlanDev *fdev, const SosPlanDev *e
     memset(&b, 0, sizeof(b));
     b.in = SF > 0 ? yf : x; b.in_pitch = SF > 0 ? yf_pitch : x_pitch;
     b.out = env; b.out_pitch = env_pitch;
-    b.ckpt = (const double *)work; b.ckpt_pitch = ckpt_pitch;
-    b.T = frames; b.skip = skip; b.n_tiles = n_tiles; b.edge = edge;
+    b.ckpt = (const double *)work; b.ckpt_pitch = ts.ckpt_pitch;
+    b.T = frames; b.skip = skip; b.n_tiles = ts.n_tiles; b.edge = edge;
     b.lead = gs.lead; b.env0 = gs.env0;
     b.rectify = rectify; b.clamp = clamp; b.gain = rectify ? gain : 1.0;
     b.trace = ctx->sos_trace;
     b.trace_rows = ctx->sos_trace_rows;
     b.debug = ctx->sos_debug;
     b.fair = ctx->sos_fair;
-    const long long used_tiles = n_tiles - skip / TILE;      // tiles below `skip` are never visited
+    const long long used_tiles = ts.n_tiles - skip / TILE;      // tiles below `skip` are never visited
     long long seg_len = 0;
     plan_segments(ctx, used_tiles * TILE, channels, warmE, &seg_len, &b.n_seg, 4, SE <= 2 ? 8 : 16);   // env_bwd_kernel: REGW
     b.seg_tiles = seg_len / TILE;
@@ -1121,9 +1113,7 @@ int hipdsp_sosplan_upload(hipdsp_ctx *ctx, hipdsp_sosplan *plan)
     HD_REQUIRE(plan->host->n_sections > 0, "plan has no coefficients yet");
     HD_CHECK_HIP(hipMemcpyAsync(plan->dev, plan->host, sizeof(SosPlanDev), hipMemcpyHostToDevice,
                                 ctx->stream));
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (ctx->stream) (void)hipStreamIsCapturing(ctx->stream, &st);
-    if (st == hipStreamCaptureStatusNone) {
+    if (!hd_capturing(ctx)) {
         HD_CHECK_HIP(hipEventRecord(plan->uploaded, ctx->stream));
         plan->valid = true;
     }

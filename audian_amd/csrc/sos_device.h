@@ -319,6 +319,19 @@ inline void hd_note_sweep(hipdsp_ctx *ctx, long long lead, long long env0, long 
     ctx->sweep_sections = SE;
 }
 
+// Where a forward sweep parks the envelope's tile states in the context scratch and where the backward sweeps -- other
+// entry points -- look for them: per channel `ckpt_pitch` doubles, 2 * SE per tile of the T + edge samples the sweep
+// walks, + 1 slot behind the last tile for the state the channel ends with (FloodArgs: NaN there = NaN everywhere).
+struct TileStates {
+    long long n_tiles, ckpt_pitch;
+    size_t bytes(long long channels) const { return sizeof(double) * (size_t)ckpt_pitch * (size_t)channels; }
+};
+inline TileStates hd_tile_states(long long T, int edge, int SE)
+{
+    const long long n_tiles = (T + edge + TILE - 1) / TILE;
+    return TileStates{n_tiles, (n_tiles + 1) * 2 * SE};
+}
+
 // The first tile of an envelope that starts inside it, at sample q of the tile (see GridShift): the tile holds the
 // rectified trace r; writes scipy's left odd extension ext[i] = 2 r(q) - r(q + edge - i), i < edge
 // (scipy/signal/_arraytools.py:99-107) into samples q - edge .. q - 1 and ext[0] into everything in front of them,
@@ -387,6 +400,17 @@ __global__ void zero_rows_kernel(float *__restrict__ y, long long y_pitch, long 
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
          i += (long long)gridDim.x * blockDim.x)
         yo[i] = value;
+}
+
+// what every forward sweep tells the flood: its segment flags and the filtered trace (the fused sweep adds its PSD)
+inline FloodArgs hd_flood_args(const unsigned char *flags, int n_seg, long long seg_len, float *y, long long y_pitch, long long T,
+                               long long skip)
+{
+    FloodArgs fl;
+    memset(&fl, 0, sizeof(fl));
+    fl.flags = flags; fl.n_seg = n_seg; fl.seg_len = seg_len;
+    fl.y = y; fl.y_pitch = y_pitch; fl.T = T; fl.skip = skip;
+    return fl;
 }
 
 // a forward sweep without an envelope behind it (no env_fix_kernel to ride on): the flood as a launch of its own

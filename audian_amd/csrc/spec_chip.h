@@ -392,21 +392,17 @@ __global__ __launch_bounds__(512, 2) void spec_chip_kernel(
 }
 
 template <bool X2>
-inline int run_chip(hipdsp_ctx *ctx, const float *x, long long x_pitch, long long channels, long long n_valid,
-                    long long frames_out, long long out_pitch, int hop, float scale, float *out, float *db_out)
+inline int run_chip(const SpecJob &j)
 {
     // (a run of ONE frame: neighbours in time are then neighbours on the XCD, and the half they share is in L2; a longer run
     // only amortises a thread's five base twiddles and re-reads its own shared halves 30 us later, from HBM)
-    long long fpb = (!X2 && ctx->spec_fpw > 0) ? ctx->spec_fpw : 1;
+    long long fpb = (!X2 && j.ctx->spec_fpw > 0) ? j.ctx->spec_fpw : 1;
     if (fpb > 16) fpb = 16;
-    const long long runs = (frames_out + fpb - 1) / fpb, total = runs * channels * (X2 ? 2 : 1);
+    const long long runs = (j.frames_out + fpb - 1) / fpb, total = runs * j.channels * (X2 ? 2 : 1);
     HD_REQUIRE(total <= 0x7ffffff0LL, "too many frames");
     const dim3 grid((unsigned)(((total + 7) / 8) * 8));
-    if (db_out)
-        hipLaunchKernelGGL((spec_chip_kernel<true, X2>), grid, dim3(512), 0, ctx->stream, x, x_pitch, n_valid, frames_out,
-                           out_pitch, hop, scale, out, db_out, (int)fpb, runs, total);
-    else
-        hipLaunchKernelGGL((spec_chip_kernel<false, X2>), grid, dim3(512), 0, ctx->stream, x, x_pitch, n_valid, frames_out,
-                           out_pitch, hop, scale, out, db_out, (int)fpb, runs, total);
+    const auto kernel = j.db_out ? spec_chip_kernel<true, X2> : spec_chip_kernel<false, X2>;
+    hipLaunchKernelGGL(kernel, grid, dim3(512), 0, j.ctx->stream, j.x, j.x_pitch, j.n_valid, j.frames_out, j.out_pitch,
+                       j.hop, j.scale, j.out, j.db_out, (int)fpb, runs, total);
     return hd_launch_status("spec_chip_kernel");
 }

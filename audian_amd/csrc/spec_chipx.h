@@ -356,17 +356,13 @@ __global__ __launch_bounds__(512, 2) void spec_chipx_kernel(
 }
 
 template <int RX>
-inline int run_chipx(hipdsp_ctx *ctx, const float *x, long long x_pitch, long long channels, long long n_valid,
-                     long long frames_out, long long out_pitch, int hop, float scale, float *out, float *db_out)
+inline int run_chipx(const SpecJob &j)
 {
-    const long long total = frames_out * channels * (RX / 2 + 1);
+    const long long total = j.frames_out * j.channels * (RX / 2 + 1);
     HD_REQUIRE(total <= 0x7ffffff0LL, "too many frames");
     const dim3 grid((unsigned)(((total + 7) / 8) * 8));
-    if (db_out)
-        hipLaunchKernelGGL((spec_chipx_kernel<true, RX>), grid, dim3(512), 0, ctx->stream, x, x_pitch, n_valid, frames_out,
-                           out_pitch, hop, scale, out, db_out, total);
-    else
-        hipLaunchKernelGGL((spec_chipx_kernel<false, RX>), grid, dim3(512), 0, ctx->stream, x, x_pitch, n_valid, frames_out,
-                           out_pitch, hop, scale, out, db_out, total);
+    const auto kernel = j.db_out ? spec_chipx_kernel<true, RX> : spec_chipx_kernel<false, RX>;
+    hipLaunchKernelGGL(kernel, grid, dim3(512), 0, j.ctx->stream, j.x, j.x_pitch, j.n_valid, j.frames_out, j.out_pitch,
+                       j.hop, j.scale, j.out, j.db_out, total);
     return hd_launch_status("spec_chipx_kernel");
 }

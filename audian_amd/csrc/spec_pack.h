@@ -400,26 +400,22 @@ __global__ __launch_bounds__(256, NFFT >= 1024 ? 2 : 3) void spec_pack_kernel(
 // batches of G frames one wave walks: long runs amortise the table load and the first fetch, short ones keep small
 // inputs spread over the chip (12 waves per CU resident)
 template <int NFFT, int LPF, int R1, int R2, int R3>
-int run_pack(hipdsp_ctx *ctx, const float *x, long long x_pitch, long long channels, long long frames, long long n_valid,
-             long long frames_out, long long out_pitch, int hop, float scale, float *out, float *db_out)
+int run_pack(const SpecJob &j)
 {
     const float *tables = nullptr;
-    int rc = R3 > 1 ? fft_tables(ctx, NFFT, R1, R2, R3, &tables) : fft_tables2(ctx, NFFT, R1, R2, &tables);
+    int rc = hd_fft_table_set(j.ctx, NFFT, R1, R2, R3 > 1 ? R3 : 0, &tables);       // (R3 == 1: the two-stage set)
     if (rc != HIPDSP_OK) return rc;
     constexpr int G = 64 / LPF;
-    const long long batches = (frames_out + G - 1) / G;
-    long long bpw = ctx->spec_fpw > 0 ? ctx->spec_fpw : channels * batches / ((long long)ctx->n_cus * 48);
+    const long long batches = (j.frames_out + G - 1) / G;
+    long long bpw = j.ctx->spec_fpw > 0 ? j.ctx->spec_fpw : j.channels * batches / ((long long)j.ctx->n_cus * 48);
     if (bpw < 1) bpw = 1;
     if (bpw > 64) bpw = 64;
     const long long per_block = 4 * bpw;
     const long long bx = (batches + per_block - 1) / per_block;
     HD_REQUIRE(bx <= 0x7fffffffLL, "grid too large");
-    const dim3 grid((unsigned)bx, (unsigned)channels), block(256);
-    if (db_out)
-        hipLaunchKernelGGL((spec_pack_kernel<NFFT, LPF, R1, R2, R3, true>), grid, block, 0, ctx->stream, x, x_pitch, frames,
-                           n_valid, frames_out, out_pitch, hop, scale, tables, out, db_out, (int)bpw, ctx->spec_debug);
-    else
-        hipLaunchKernelGGL((spec_pack_kernel<NFFT, LPF, R1, R2, R3, false>), grid, block, 0, ctx->stream, x, x_pitch, frames,
-                           n_valid, frames_out, out_pitch, hop, scale, tables, out, db_out, (int)bpw, ctx->spec_debug);
+    const dim3 grid((unsigned)bx, (unsigned)j.channels), block(256);
+    const auto kernel = j.db_out ? spec_pack_kernel<NFFT, LPF, R1, R2, R3, true> : spec_pack_kernel<NFFT, LPF, R1, R2, R3, false>;
+    hipLaunchKernelGGL(kernel, grid, block, 0, j.ctx->stream, j.x, j.x_pitch, j.frames, j.n_valid, j.frames_out, j.out_pitch,
+                       j.hop, j.scale, tables, j.out, j.db_out, (int)bpw, j.ctx->spec_debug);
     return hd_launch_status("spec_pack_kernel");
 }

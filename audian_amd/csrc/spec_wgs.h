@@ -343,22 +343,21 @@ __global__ __launch_bounds__(LPF, OCC) void spec_wgs_kernel(
 }
 
 template <int NFFT, int LPF, int R1, int R2, int R3, int OCC>
-int run_wgs(hipdsp_ctx *ctx, const float *x, long long x_pitch, long long channels, long long n_valid,
-            long long frames_out, long long out_pitch, int hop, float scale, float *out, float *db_out)
+int run_wgs(const SpecJob &j)
 {
     const float *tables = nullptr;
-    int rc = fft_tables(ctx, NFFT, R1, R2, R3, &tables);
+    int rc = hd_fft_table_set(j.ctx, NFFT, R1, R2, R3, &tables);
     if (rc != HIPDSP_OK) return rc;
     // long runs of frames per workgroup once there are many more frames than the chip holds workgroups
-    long long fpb = ctx->spec_fpw > 0 ? ctx->spec_fpw : frames_out * channels / ((long long)ctx->n_cus * 4 * OCC);
+    long long fpb = j.ctx->spec_fpw > 0 ? j.ctx->spec_fpw : j.frames_out * j.channels / ((long long)j.ctx->n_cus * 4 * OCC);
     if (fpb < 1) fpb = 1;
     if (fpb > 32) fpb = 32;
-    const dim3 grid((unsigned)((frames_out + fpb - 1) / fpb), (unsigned)channels);
-    const bool half = hop * 2 == NFFT;
-#define HD_WGS(DBV, HALFV)                                                                                                 \
-    hipLaunchKernelGGL((spec_wgs_kernel<NFFT, LPF, R1, R2, R3, OCC, DBV, HALFV>), grid, dim3(LPF), 0, ctx->stream, x, x_pitch, \
-                       n_valid, frames_out, out_pitch, hop, scale, tables, out, db_out, (int)fpb)
-    if (db_out) { if (half) HD_WGS(true, true); else HD_WGS(true, false); }
+    const dim3 grid((unsigned)((j.frames_out + fpb - 1) / fpb), (unsigned)j.channels);
+    const bool half = j.hop * 2 == NFFT;
+#define HD_WGS(DBV, HALFV)                                                                                        \
+    hipLaunchKernelGGL((spec_wgs_kernel<NFFT, LPF, R1, R2, R3, OCC, DBV, HALFV>), grid, dim3(LPF), 0, j.ctx->stream, \
+                       j.x, j.x_pitch, j.n_valid, j.frames_out, j.out_pitch, j.hop, j.scale, tables, j.out, j.db_out, (int)fpb)
+    if (j.db_out) { if (half) HD_WGS(true, true); else HD_WGS(true, false); }
     else { if (half) HD_WGS(false, true); else HD_WGS(false, false); }
 #undef HD_WGS
     return hd_launch_status("spec_wgs_kernel");

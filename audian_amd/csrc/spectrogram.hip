@@ -966,21 +966,33 @@ __global__ void big_zero_tail_kernel(float *__restrict__ out, float *__restrict_
     }
 }
 
-int run_big(hipdsp_ctx *ctx, const float *x, long long x_pitch, long long channels, long long n_valid,
-            long long frames_out, long long out_pitch, int nfft, int hop, float scale, float *out, float *db_out)
+// One call of hipdsp_spectrogram as its launchers see it, filled once the frame count and the PSD scale are known.
+struct SpecJob {
+    hipdsp_ctx *ctx;
+    const float *x;
+    long long x_pitch, channels, frames;
+    long long n_valid;             // frames inside the trace (hd_frames_valid); the rest of frames_out is the zero tail
+    long long frames_out, out_pitch;
+    int hop;
+    float scale;                   // 1 / (fs * hd_hann_sumsq(nfft))
+    float *out, *db_out;           // db_out may be NULL
+};
+
+int run_big(const SpecJob &j, int nfft)
 {
+    hipdsp_ctx *ctx = j.ctx;
     const int M = nfft / 2;
     int m = 0;
     while ((1 << m) < M) m++;
     const int N1 = 1 << ((m + 1) / 2), N2 = 1 << (m / 2);
     const long long F = (long long)M + 1;
-    if (frames_out > n_valid) {
-        hipLaunchKernelGGL(big_zero_tail_kernel, dim3(256, (unsigned)channels), dim3(256), 0, ctx->stream, out, db_out,
-                           out_pitch, F, n_valid, frames_out);
+    if (j.frames_out > j.n_valid) {
+        hipLaunchKernelGGL(big_zero_tail_kernel, dim3(256, (unsigned)j.channels), dim3(256), 0, ctx->stream, j.out, j.db_out,
+                           j.out_pitch, F, j.n_valid, j.frames_out);
         int rc = hd_launch_status("big_zero_tail_kernel");
         if (rc != HIPDSP_OK) return rc;
     }
-    const long long items = channels * n_valid;
+    const long long items = j.channels * j.n_valid;
     if (items == 0) return HIPDSP_OK;
     // scratch: mean | B | Z for one batch of (channel, frame) items, at most ~512 MiB
     long long batch = (512LL << 20) / (16LL * M + 8);
@@ -1000,12 +1012,12 @@ int run_big(hipdsp_ctx *ctx, const float *x, long long x_pitch, long long channe
     HD_CHECK_HIP(hipFuncSetAttribute((const void *)big_pass2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
     for (long long item0 = 0; item0 < items; item0 += batch) {
         const unsigned nb = (unsigned)(items - item0 < batch ? items - item0 : batch);
-        hipLaunchKernelGGL(big_mean_kernel, dim3(nb), dim3(256), 0, ctx->stream, x, x_pitch, n_valid, item0, nfft, hop, mean);
-        hipLaunchKernelGGL(big_pass1_kernel, dim3((unsigned)(N2 / BIG_W), nb), dim3(256), lds1, ctx->stream, x, x_pitch,
-                           n_valid, item0, nfft, hop, N1, N2, mean, B);
+        hipLaunchKernelGGL(big_mean_kernel, dim3(nb), dim3(256), 0, ctx->stream, j.x, j.x_pitch, j.n_valid, item0, nfft, j.hop, mean);
+        hipLaunchKernelGGL(big_pass1_kernel, dim3((unsigned)(N2 / BIG_W), nb), dim3(256), lds1, ctx->stream, j.x, j.x_pitch,
+                           j.n_valid, item0, nfft, j.hop, N1, N2, mean, B);
         hipLaunchKernelGGL(big_pass2_kernel, dim3((unsigned)(N1 / BIG_W), nb), dim3(256), lds2, ctx->stream, B, M, N1, N2, Z);
         hipLaunchKernelGGL(big_split_kernel, dim3((unsigned)((M / 2 + 1 + 255) / 256), nb), dim3(256), 0, ctx->stream, Z, M,
-                           n_valid, frames_out, out_pitch, item0, scale, out, db_out);
+                           j.n_valid, j.frames_out, j.out_pitch, item0, j.scale, j.out, j.db_out);
         rc = hd_launch_status("big spectrogram kernels");
         if (rc != HIPDSP_OK) return rc;
     }
@@ -1025,155 +1037,60 @@ int frames_per_wave(const hipdsp_ctx *ctx, long long channels, long long frames_
 }
 
 template <int NFFT, int LPF, int R1, int R2, int R3, int WAVES>
-int launch_fast(hipdsp_ctx *ctx, const float *x, long long x_pitch, long long channels, long long n_valid,
-                long long frames_out, long long out_pitch, int hop, float scale, const float *tables,
-                float *out, float *db_out)
+int launch_fast(const SpecJob &j, const float *tables)
 {
     constexpr int G = 64 / LPF;
-    const int fpw = frames_per_wave(ctx, channels, frames_out, G);
+    const int fpw = frames_per_wave(j.ctx, j.channels, j.frames_out, G);
     long long per_block = (long long)WAVES * fpw * G;
-    long long bx = (frames_out + per_block - 1) / per_block;
+    long long bx = (j.frames_out + per_block - 1) / per_block;
     // 50 % / 75 % overlap with one frame per wave: reuse the overlapped half / three quarters from registers
     // (measured, tools/spec_reuse_ab.py, 64 ch x 120 s: 1024/256 3.17 -> 3.92 TB/s, 2048/512 3.29 -> 3.66, 1024/512
     // 4.28 -> 4.54, 2048/1024 equal; at nfft 4096 -- one workgroup per CU -- the rotating register sets cost
     // more than the saved requests: 3.46 -> 2.75 TB/s at hop 2048, so that size fetches every frame whole)
-    const int reuse = (LPF != 64 || NFFT > 2048 || ctx->spec_no_half) ? 1
-                                                                      : (hop * 2 == NFFT ? 2 : (hop * 4 == NFFT ? 4 : 1));
-    dim3 grid((unsigned)bx, (unsigned)channels), block(64 * WAVES);
-#define HD_SPEC_LAUNCH(DBV, REUSEV)                                                                 \
-    hipLaunchKernelGGL((spec_fast_kernel<NFFT, LPF, R1, R2, R3, WAVES, DBV, REUSEV>), grid, block, 0, \
-                       ctx->stream, x, x_pitch, n_valid, frames_out, out_pitch, hop, scale, tables,   \
-                       out, db_out, fpw)
+    const int reuse = (LPF != 64 || NFFT > 2048 || j.ctx->spec_no_half) ? 1
+                                                                        : (j.hop * 2 == NFFT ? 2 : (j.hop * 4 == NFFT ? 4 : 1));
+    dim3 grid((unsigned)bx, (unsigned)j.channels), block(64 * WAVES);
+#define HD_SPEC_LAUNCH(DBV, REUSEV)                                                                           \
+    hipLaunchKernelGGL((spec_fast_kernel<NFFT, LPF, R1, R2, R3, WAVES, DBV, REUSEV>), grid, block, 0,         \
+                       j.ctx->stream, j.x, j.x_pitch, j.n_valid, j.frames_out, j.out_pitch, j.hop, j.scale, \
+                       tables, j.out, j.db_out, fpw)
     if (LPF == 64 && reuse == 2) {
-        if (db_out) HD_SPEC_LAUNCH(true, (LPF == 64 ? 2 : 1));
+        if (j.db_out) HD_SPEC_LAUNCH(true, (LPF == 64 ? 2 : 1));
         else HD_SPEC_LAUNCH(false, (LPF == 64 ? 2 : 1));
     } else if (LPF == 64 && reuse == 4) {
-        if (db_out) HD_SPEC_LAUNCH(true, (LPF == 64 ? 4 : 1));
+        if (j.db_out) HD_SPEC_LAUNCH(true, (LPF == 64 ? 4 : 1));
         else HD_SPEC_LAUNCH(false, (LPF == 64 ? 4 : 1));
     } else {
-        if (db_out) HD_SPEC_LAUNCH(true, 1);
+        if (j.db_out) HD_SPEC_LAUNCH(true, 1);
         else HD_SPEC_LAUNCH(false, 1);
     }
 #undef HD_SPEC_LAUNCH
     return hd_launch_status("spec_fast_kernel");
 }
 
-// tw2 | tw3 | twn | window for one nfft, computed in float64 on the host in the order the
-// kernel keeps them in LDS
-int fft_tables(hipdsp_ctx *ctx, int nfft, int R1, int R2, int R3, const float **dev)
-{
-    int lg = 0;
-    while ((1 << lg) < nfft) lg++;
-    if (!ctx->fft_tables[lg]) {
-        const int M = nfft / 2;
-        const int TW2 = (R2 - 1) * R1, TW3 = R1 * R2, TWN = M / 2 + 1;
-        size_t n = 2 * (size_t)(TW2 + TW3 + TWN + M);
-        float *h = new float[n];
-        float *p = h;
-        for (int t = 1; t < R2; t++)
-            for (int k = 0; k < R1; k++) {
-                double a = -2.0 * M_PI * (double)(k * t) / (double)(R1 * R2);
-                *p++ = (float)cos(a); *p++ = (float)sin(a);
-            }
-        for (int k = 0; k < R1 * R2; k++) {
-            double a = -2.0 * M_PI * (double)k / (double)M;
-            *p++ = (float)cos(a); *p++ = (float)sin(a);
-        }
-        (void)R3;
-        for (int k = 0; k <= M / 2; k++) {
-            double a = -2.0 * M_PI * (double)k / (double)nfft;
-            *p++ = (float)cos(a); *p++ = (float)sin(a);
-        }
-        for (int i = 0; i < nfft; i++) *p++ = (float)(0.5 - 0.5 * cos(2.0 * M_PI * (double)i / (double)nfft));
-        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-        if (ctx->stream) (void)hipStreamIsCapturing(ctx->stream, &st);
-        if (st != hipStreamCaptureStatusNone) {
-            delete[] h;
-            hipdsp_set_error("first spectrogram call for nfft %d during stream capture; run it once before", nfft);
-            return HIPDSP_ERR_INVALID;
-        }
-        void *d = nullptr;
-        hipError_t e = hipMalloc(&d, n * sizeof(float));
-        if (e == hipSuccess) e = hipMemcpy(d, h, n * sizeof(float), hipMemcpyHostToDevice);
-        delete[] h;
-        if (e != hipSuccess) {
-            if (d) (void)hipFree(d);
-            HD_CHECK_HIP(e);
-        }
-        ctx->fft_tables[lg] = d;
-    }
-    *dev = (const float *)ctx->fft_tables[lg];
-    return HIPDSP_OK;
-}
-
-// tw2 | twn | window for the two-stage kernel
-int fft_tables2(hipdsp_ctx *ctx, int nfft, int R1, int R2, const float **dev)
-{
-    int lg = 0;
-    while ((1 << lg) < nfft) lg++;
-    if (!ctx->fft_tables2[lg]) {
-        const int M = nfft / 2;
-        const int TW2 = (R2 - 1) * R1, TWN = M / 2 + 1;
-        size_t n = 2 * (size_t)(TW2 + TWN + M);
-        float *h = new float[n];
-        float *p = h;
-        for (int t = 1; t < R2; t++)
-            for (int k = 0; k < R1; k++) {
-                double a = -2.0 * M_PI * (double)(k * t) / (double)M;
-                *p++ = (float)cos(a); *p++ = (float)sin(a);
-            }
-        for (int k = 0; k <= M / 2; k++) {
-            double a = -2.0 * M_PI * (double)k / (double)nfft;
-            *p++ = (float)cos(a); *p++ = (float)sin(a);
-        }
-        for (int i = 0; i < nfft; i++) *p++ = (float)(0.5 - 0.5 * cos(2.0 * M_PI * (double)i / (double)nfft));
-        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-        if (ctx->stream) (void)hipStreamIsCapturing(ctx->stream, &st);
-        if (st != hipStreamCaptureStatusNone) {
-            delete[] h;
-            hipdsp_set_error("first spectrogram call for nfft %d during stream capture; run it once before", nfft);
-            return HIPDSP_ERR_INVALID;
-        }
-        void *d = nullptr;
-        hipError_t e = hipMalloc(&d, n * sizeof(float));
-        if (e == hipSuccess) e = hipMemcpy(d, h, n * sizeof(float), hipMemcpyHostToDevice);
-        delete[] h;
-        if (e != hipSuccess) {
-            if (d) (void)hipFree(d);
-            HD_CHECK_HIP(e);
-        }
-        ctx->fft_tables2[lg] = d;
-    }
-    *dev = (const float *)ctx->fft_tables2[lg];
-    return HIPDSP_OK;
-}
-
 template <int NFFT, int LPF, int R1, int R2, int WAVES>
-int run_fast2(hipdsp_ctx *ctx, const float *x, long long x_pitch, long long channels, long long n_valid,
-              long long frames_out, long long out_pitch, int hop, float scale, float *out, float *db_out)
+int run_fast2(const SpecJob &j)
 {
     const float *tables = nullptr;
-    int rc = fft_tables2(ctx, NFFT, R1, R2, &tables);
+    int rc = hd_fft_table_set(j.ctx, NFFT, R1, R2, 0, &tables);
     if (rc != HIPDSP_OK) return rc;
     constexpr int G = 64 / LPF;
-    const int fpw = frames_per_wave(ctx, channels, frames_out, G);
+    const int fpw = frames_per_wave(j.ctx, j.channels, j.frames_out, G);
     long long per_block = (long long)WAVES * G * fpw;
-    long long bx = (frames_out + per_block - 1) / per_block;
-    hipLaunchKernelGGL((spec2_kernel<NFFT, LPF, R1, R2, WAVES>), dim3((unsigned)bx, (unsigned)channels),
-                       dim3(64 * WAVES), 0, ctx->stream, x, x_pitch, n_valid, frames_out, out_pitch, hop, scale,
-                       tables, out, db_out, fpw);
+    long long bx = (j.frames_out + per_block - 1) / per_block;
+    hipLaunchKernelGGL((spec2_kernel<NFFT, LPF, R1, R2, WAVES>), dim3((unsigned)bx, (unsigned)j.channels),
+                       dim3(64 * WAVES), 0, j.ctx->stream, j.x, j.x_pitch, j.n_valid, j.frames_out, j.out_pitch, j.hop,
+                       j.scale, tables, j.out, j.db_out, fpw);
     return hd_launch_status("spec2_kernel");
 }
 
 template <int NFFT, int LPF, int R1, int R2, int R3, int WAVES>
-int run_fast(hipdsp_ctx *ctx, const float *x, long long x_pitch, long long channels, long long n_valid,
-             long long frames_out, long long out_pitch, int hop, float scale, float *out, float *db_out)
+int run_fast(const SpecJob &j)
 {
     const float *tables = nullptr;
-    int rc = fft_tables(ctx, NFFT, R1, R2, R3, &tables);
+    int rc = hd_fft_table_set(j.ctx, NFFT, R1, R2, R3, &tables);
     if (rc != HIPDSP_OK) return rc;
-    return launch_fast<NFFT, LPF, R1, R2, R3, WAVES>(ctx, x, x_pitch, channels, n_valid, frames_out, out_pitch,
-                                                     hop, scale, tables, out, db_out);
+    return launch_fast<NFFT, LPF, R1, R2, R3, WAVES>(j, tables);
 }
 
 #include "spec_pack.h"
@@ -1182,37 +1099,23 @@ int run_fast(hipdsp_ctx *ctx, const float *x, long long x_pitch, long long chann
 #include "spec_chipx.h"
 
 template <int NFFT, int LPF, int R1, int R2, int R3, int OCC>
-int run_wg(hipdsp_ctx *ctx, const float *x, long long x_pitch, long long channels, long long n_valid,
-           long long frames_out, long long out_pitch, int hop, float scale, float *out, float *db_out)
+int run_wg(const SpecJob &j)
 {
     const float *tables = nullptr;
-    int rc = fft_tables(ctx, NFFT, R1, R2, R3, &tables);
+    int rc = hd_fft_table_set(j.ctx, NFFT, R1, R2, R3, &tables);
     if (rc != HIPDSP_OK) return rc;
     // a few frames per workgroup once there are many more frames than the chip holds workgroups
-    long long fpb = frames_out * channels / ((long long)ctx->n_cus * 8);
+    long long fpb = j.frames_out * j.channels / ((long long)j.ctx->n_cus * 8);
     if (fpb < 1) fpb = 1;
     if (fpb > 8) fpb = 8;
-    const dim3 grid((unsigned)((frames_out + fpb - 1) / fpb), (unsigned)channels);
-    if (db_out)
-        hipLaunchKernelGGL((spec_wg_kernel<NFFT, LPF, R1, R2, R3, OCC, true>), grid, dim3(LPF), 0, ctx->stream, x, x_pitch,
-                           n_valid, frames_out, out_pitch, hop, scale, tables, out, db_out, (int)fpb);
-    else
-        hipLaunchKernelGGL((spec_wg_kernel<NFFT, LPF, R1, R2, R3, OCC, false>), grid, dim3(LPF), 0, ctx->stream, x, x_pitch,
-                           n_valid, frames_out, out_pitch, hop, scale, tables, out, db_out, (int)fpb);
+    const dim3 grid((unsigned)((j.frames_out + fpb - 1) / fpb), (unsigned)j.channels);
+    const auto kernel = j.db_out ? spec_wg_kernel<NFFT, LPF, R1, R2, R3, OCC, true> : spec_wg_kernel<NFFT, LPF, R1, R2, R3, OCC, false>;
+    hipLaunchKernelGGL(kernel, grid, dim3(LPF), 0, j.ctx->stream, j.x, j.x_pitch, j.n_valid, j.frames_out, j.out_pitch,
+                       j.hop, j.scale, tables, j.out, j.db_out, (int)fpb);
     return hd_launch_status("spec_wg_kernel");
 }
 
 }  // namespace
-
-int hd_fft_tables(hipdsp_ctx *ctx, int nfft, const float **dev)
-{
-    if (nfft == 2048) return fft_tables(ctx, 2048, 16, 16, 4, dev);
-    if (nfft == 1024) return fft_tables(ctx, 1024, 8, 8, 8, dev);
-    if (nfft == 512) return fft_tables(ctx, 512, 8, 8, 4, dev);
-    if (nfft == 256) return fft_tables(ctx, 256, 8, 4, 4, dev);
-    hipdsp_set_error("no three-stage table set for nfft %d", nfft);
-    return HIPDSP_ERR_UNSUPPORTED;
-}
 
 extern "C" int hipdsp_spectrogram(hipdsp_ctx *ctx, const float *x, int64_t x_pitch, int64_t channels,
                                   int64_t frames, int nfft, int hop, double fs, float *out,
@@ -1236,12 +1139,7 @@ extern "C" int hipdsp_spectrogram(hipdsp_ctx *ctx, const float *x, int64_t x_pit
     HD_REQUIRE(channels <= 65535, "more than 65535 channels");
     HD_REQUIRE(frames_out <= 0x7fffffffLL, "too many frames");
     HD_CHECK_HIP(hipSetDevice(ctx->device));
-    // bufferedspectrogram.py:46-49 and scipy _spectral_helper segment count
-    long long nsource = (frames_out - 1) * (long long)hop + nfft;
-    if (nsource > frames) nsource = frames;
-    long long n_valid = 0;
-    if (nsource >= nfft) n_valid = (nsource - (nfft - hop)) / hop;
-    if (n_valid > frames_out) n_valid = frames_out;
+    const long long n_valid = hd_frames_valid(frames_out, frames, nfft, hop);
     if (n_valid > 0) HD_REQUIRE(x != nullptr && x_pitch >= frames, "bad input");
     if (n_valid == 0) {
         // a slab shorter than one window (bufferedspectrogram.py:47-49: dest[:] = 0): nothing may read x -- the
@@ -1251,12 +1149,8 @@ extern "C" int hipdsp_spectrogram(hipdsp_ctx *ctx, const float *x, int64_t x_pit
                            (long long)out_pitch, (long long)(nfft / 2 + 1), 0LL, (long long)frames_out);
         return hd_launch_status("big_zero_tail_kernel");
     }
-    double wss = 0.0;
-    for (int i = 0; i < nfft; i++) {
-        double w = 0.5 - 0.5 * cos(2.0 * M_PI * (double)i / (double)nfft);
-        wss += w * w;
-    }
-    float scale = (float)(1.0 / (fs * wss));
+    const float scale = (float)(1.0 / (fs * hd_hann_sumsq(nfft)));
+    const SpecJob job{ctx, x, x_pitch, channels, frames, n_valid, frames_out, out_pitch, hop, scale, out, db_out};
     if (!pow2) {
         HD_REQUIRE(frames_out <= 65535, "too many frames for the direct DFT path");
         hipLaunchKernelGGL(spec_direct_kernel, dim3((unsigned)((nfft / 2 + 1 + 255) / 256), (unsigned)frames_out,
@@ -1272,77 +1166,66 @@ extern "C" int hipdsp_spectrogram(hipdsp_ctx *ctx, const float *x, int64_t x_pit
         // short windows: 64 (one frame per lane), 32, 16, 8 or 4 frames side by side in a wave that streams a run of
         // consecutive frames through LDS (spec_pack.h); "spec_kernel" 2 / 3: the kernels they replaced, as cross-checks
         case 8:
-            if (want == 2) return run_fast2<8, 1, 2, 2, 4>(ctx, x, x_pitch, channels, n_valid, frames_out, out_pitch, hop, scale, out, db_out);
-            return run_pack<8, 1, 2, 2, 1>(ctx, x, x_pitch, channels, frames, n_valid, frames_out, out_pitch, hop, scale, out, db_out);
+            if (want == 2) return run_fast2<8, 1, 2, 2, 4>(job);
+            return run_pack<8, 1, 2, 2, 1>(job);
         case 16:
-            if (want == 2) return run_fast2<16, 1, 4, 2, 4>(ctx, x, x_pitch, channels, n_valid, frames_out, out_pitch, hop, scale, out, db_out);
-            return run_pack<16, 1, 4, 2, 1>(ctx, x, x_pitch, channels, frames, n_valid, frames_out, out_pitch, hop, scale, out, db_out);
+            if (want == 2) return run_fast2<16, 1, 4, 2, 4>(job);
+            return run_pack<16, 1, 4, 2, 1>(job);
         case 32:
-            if (want == 2) return run_fast2<32, 2, 8, 2, 4>(ctx, x, x_pitch, channels, n_valid, frames_out, out_pitch, hop, scale, out, db_out);
-            return run_pack<32, 2, 8, 2, 1>(ctx, x, x_pitch, channels, frames, n_valid, frames_out, out_pitch, hop, scale, out, db_out);
+            if (want == 2) return run_fast2<32, 2, 8, 2, 4>(job);
+            return run_pack<32, 2, 8, 2, 1>(job);
         case 64:
-            if (want == 2) return run_fast2<64, 4, 8, 4, 4>(ctx, x, x_pitch, channels, n_valid, frames_out, out_pitch, hop, scale, out, db_out);
-            return run_pack<64, 4, 8, 4, 1>(ctx, x, x_pitch, channels, frames, n_valid, frames_out, out_pitch, hop, scale, out, db_out);
+            if (want == 2) return run_fast2<64, 4, 8, 4, 4>(job);
+            return run_pack<64, 4, 8, 4, 1>(job);
         case 128:
-            if (want == 2) return run_fast2<128, 8, 8, 8, 4>(ctx, x, x_pitch, channels, n_valid, frames_out, out_pitch, hop, scale, out, db_out);
-            return run_pack<128, 8, 8, 8, 1>(ctx, x, x_pitch, channels, frames, n_valid, frames_out, out_pitch, hop, scale, out, db_out);
+            if (want == 2) return run_fast2<128, 8, 8, 8, 4>(job);
+            return run_pack<128, 8, 8, 8, 1>(job);
         case 256:
-            if (want == 2) return run_fast2<256, 8, 16, 8, 4>(ctx, x, x_pitch, channels, n_valid, frames_out, out_pitch, hop, scale, out, db_out);
-            if (want == 3) return run_fast<256, 16, 8, 4, 4, 4>(ctx, x, x_pitch, channels, n_valid, frames_out, out_pitch, hop, scale, out, db_out);
-            return run_pack<256, 16, 8, 4, 4>(ctx, x, x_pitch, channels, frames, n_valid, frames_out, out_pitch, hop, scale, out, db_out);
+            if (want == 2) return run_fast2<256, 8, 16, 8, 4>(job);
+            if (want == 3) return run_fast<256, 16, 8, 4, 4, 4>(job);
+            return run_pack<256, 16, 8, 4, 4>(job);
         case 512:
-            if (want == 2) return run_fast2<512, 16, 16, 16, 4>(ctx, x, x_pitch, channels, n_valid, frames_out, out_pitch, hop, scale, out, db_out);
+            if (want == 2) return run_fast2<512, 16, 16, 16, 4>(job);
             // the stream through LDS as well (round 5: with the dB image 13 % ahead at 50 % overlap, 27 % at 75 %, 36 % at hop 100;
             // profiles/r05at_spec_kernel_ab.log) -- except for the PSD alone at 50 % overlap, where the kernel it replaces ("spec_kernel"
             // 3) is 5 % ahead
-            if (want == 3 || (want == 0 && db_out == nullptr && 2 * hop == nfft))
-                return run_fast<512, 32, 8, 8, 4, 4>(ctx, x, x_pitch, channels, n_valid, frames_out, out_pitch, hop, scale, out, db_out);
-            return run_pack<512, 32, 8, 8, 4>(ctx, x, x_pitch, channels, frames, n_valid, frames_out, out_pitch, hop, scale, out, db_out);
+            if (want == 3 || (want == 0 && db_out == nullptr && 2 * hop == nfft)) return run_fast<512, 32, 8, 8, 4, 4>(job);
+            return run_pack<512, 32, 8, 8, 4>(job);
         case 1024:
-            if (want == 2) return run_fast2<1024, 16, 32, 16, 4>(ctx, x, x_pitch, channels, n_valid, frames_out, out_pitch, hop, scale, out, db_out);
+            if (want == 2) return run_fast2<1024, 16, 32, 16, 4>(job);
             // with the dB image: the stream through LDS, whose staged 16-byte stores carry both images (separate processes, 64 ch
             // x 120 s: hop 100 12.2 -> 8.7 ms, hop 700 1.74 -> 1.53, hop = nfft 1.32 -> 1.24; in one process level to 3 % ahead at
             // every hop, nfft / 2 and nfft / 4 -- where the other kernel reuses its registers -- included: 1.96 -> 1.90, 3.55 ->
             // 3.50; without the dB image it loses 3-20 %: profiles/r05at_spec_kernel_ab.log); "spec_kernel" 3: for the PSD alone too
-            if (want == 3 || (want == 0 && db_out != nullptr))
-                return run_pack<1024, 64, 8, 8, 8>(ctx, x, x_pitch, channels, frames, n_valid, frames_out, out_pitch, hop, scale, out, db_out);
-            return run_fast<1024, 64, 8, 8, 8, 4>(ctx, x, x_pitch, channels, n_valid, frames_out, out_pitch, hop, scale, out, db_out);
+            if (want == 3 || (want == 0 && db_out != nullptr)) return run_pack<1024, 64, 8, 8, 8>(job);
+            return run_fast<1024, 64, 8, 8, 8, 4>(job);
         case 2048:
-            if (want == 2) return run_fast2<2048, 32, 32, 32, 8>(ctx, x, x_pitch, channels, n_valid, frames_out, out_pitch, hop, scale, out, db_out);
-            return run_fast<2048, 64, 16, 16, 4, 4>(ctx, x, x_pitch, channels, n_valid, frames_out, out_pitch, hop, scale, out, db_out);
+            if (want == 2) return run_fast2<2048, 32, 32, 32, 8>(job);
+            return run_fast<2048, 64, 16, 16, 4, 4>(job);
         case 4096:
-            if (want == 2) return run_wg<4096, 128, 16, 16, 8, 3>(ctx, x, x_pitch, channels, n_valid, frames_out, out_pitch, hop, scale, out, db_out);
+            if (want == 2) return run_wg<4096, 128, 16, 16, 8, 3>(job);
             // (the streamed workgroup: 3.0 TB/s, level with the one-wave-per-frame kernel, "spec_kernel" 3; 4.1 against 2.9
             // with the dB image next to the PSD)
-            if (want != 3) return run_wgs<4096, 128, 16, 16, 8, 3>(ctx, x, x_pitch, channels, n_valid, frames_out, out_pitch, hop, scale, out, db_out);
-            return run_fast<4096, 64, 16, 16, 8, 4>(ctx, x, x_pitch, channels, n_valid, frames_out, out_pitch, hop, scale, out, db_out);
+            if (want != 3) return run_wgs<4096, 128, 16, 16, 8, 3>(job);
+            return run_fast<4096, 64, 16, 16, 8, 4>(job);
         }
     }
     // long windows: a workgroup streams a run of frames through LDS (spec_wgs.h); "spec_kernel" 2: the kernel it replaced
     const bool old_wg = ctx->spec_kernel == 2;
     if (!ctx->force_generic_fft && nfft == 8192)
-        return old_wg ? run_wg<8192, 256, 16, 16, 16, 3>(ctx, x, x_pitch, channels, n_valid, frames_out, out_pitch, hop, scale, out, db_out)
-                      : run_wgs<8192, 256, 16, 16, 16, 3>(ctx, x, x_pitch, channels, n_valid, frames_out, out_pitch, hop, scale, out, db_out);
+        return old_wg ? run_wg<8192, 256, 16, 16, 16, 3>(job) : run_wgs<8192, 256, 16, 16, 16, 3>(job);
     if (!ctx->force_generic_fft && nfft == 16384)
-        return old_wg ? run_wg<16384, 256, 16, 16, 32, 2>(ctx, x, x_pitch, channels, n_valid, frames_out, out_pitch, hop, scale, out, db_out)
-                      : run_wgs<16384, 256, 16, 16, 32, 2>(ctx, x, x_pitch, channels, n_valid, frames_out, out_pitch, hop, scale, out, db_out);
+        return old_wg ? run_wg<16384, 256, 16, 16, 32, 2>(job) : run_wgs<16384, 256, 16, 16, 32, 2>(job);
     if (!ctx->force_generic_fft && nfft == 32768)
-        return old_wg
-                   ? run_wg<32768, 512, 16, 32, 32, 2>(ctx, x, x_pitch, channels, n_valid, frames_out, out_pitch, hop, scale, out, db_out)
-                      : run_wgs<32768, 512, 16, 32, 32, 1>(ctx, x, x_pitch, channels, n_valid, frames_out, out_pitch, hop, scale, out, db_out);
+        return old_wg ? run_wg<32768, 512, 16, 32, 32, 2>(job) : run_wgs<32768, 512, 16, 32, 32, 1>(job);
     // 65536: the frame in the registers of one workgroup (spec_chip.h); "spec_kernel" 2: the four-step path through HBM
-    if (!ctx->force_generic_fft && nfft == 65536 && !old_wg)
-        return run_chip<false>(ctx, x, x_pitch, channels, n_valid, frames_out, out_pitch, hop, scale, out, db_out);
+    if (!ctx->force_generic_fft && nfft == 65536 && !old_wg) return run_chip<false>(job);
     // 131072: two such workgroups per frame, one for the even and one for the odd bins
-    if (!ctx->force_generic_fft && nfft == 131072 && !old_wg)
-        return run_chip<true>(ctx, x, x_pitch, channels, n_valid, frames_out, out_pitch, hop, scale, out, db_out);
+    if (!ctx->force_generic_fft && nfft == 131072 && !old_wg) return run_chip<true>(job);
     // 262144, 524288: a radix-4 / radix-8 step in front of the same transform, the residues that pair with each other in one task
-    if (!ctx->force_generic_fft && nfft == 262144 && !old_wg)
-        return run_chipx<4>(ctx, x, x_pitch, channels, n_valid, frames_out, out_pitch, hop, scale, out, db_out);
-    if (!ctx->force_generic_fft && nfft == 524288 && !old_wg)
-        return run_chipx<8>(ctx, x, x_pitch, channels, n_valid, frames_out, out_pitch, hop, scale, out, db_out);
-    if (nfft > 8192)
-        return run_big(ctx, x, x_pitch, channels, n_valid, frames_out, out_pitch, nfft, hop, scale, out, db_out);
+    if (!ctx->force_generic_fft && nfft == 262144 && !old_wg) return run_chipx<4>(job);
+    if (!ctx->force_generic_fft && nfft == 524288 && !old_wg) return run_chipx<8>(job);
+    if (nfft > 8192) return run_big(job, nfft);
     size_t lds = sizeof(float2) * 2 * (size_t)nfft;
     if (lds > 48 * 1024)
         HD_CHECK_HIP(hipFuncSetAttribute((const void *)spec_generic_kernel,

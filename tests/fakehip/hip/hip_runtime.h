@@ -1,5 +1,6 @@
 /* A fake HIP runtime for the CPU sanitizer build of libhip_dsp's HOST-ONLY translation units (ctx.hip: context,
- * stream-ordered block cache, scratch, options; sos_plan.hip: plan mathematics, segment planner) -- test
+ * stream-ordered block cache, scratch, options; sos_plan.hip: plan mathematics, segment planner; spec_host.hip: frame
+ * count, window sum, FFT tables) -- test
  * infrastructure, tests/test_shim_sanitizers.py.  "Device" memory is host memory, streams and events are small
  * heap objects, everything completes at once; stream capture is a flag per stream so that the block cache's
  * capture rules can be exercised.  Nothing of the product is built against this header. */
@@ -56,6 +57,7 @@ static inline hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
 static inline hipError_t hipEventElapsedTime(float *ms, hipEvent_t, hipEvent_t) { *ms = 0.f; return hipSuccess; }
 /* waiting, inside a capture, for an event that was recorded outside it invalidates the capture on real HIP */
 static inline hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) { fake_hip_waits++; if (!e || !e->recorded) return hipErrorInvalidValue; if (s && s->capturing) return hipErrorInvalidValue; return hipSuccess; }
+static inline hipError_t hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind) { memmove(d, s, n); return hipSuccess; }
 static inline hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind, hipStream_t) { memmove(d, s, n); return hipSuccess; }
 static inline hipError_t hipMemsetAsync(void *d, int v, size_t n, hipStream_t) { memset(d, v, n); return hipSuccess; }
 static inline hipError_t hipMemcpy2DAsync(void *d, size_t dp, const void *s, size_t sp, size_t w, size_t h, hipMemcpyKind, hipStream_t)

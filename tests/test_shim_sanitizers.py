@@ -1,6 +1,7 @@
 """The HOST-ONLY translation units of libhip_dsp under AddressSanitizer + UndefinedBehaviorSanitizer (CPU build;
 SURVEY 5 asks for it, GPU sanitizers are not available on the pool): ctx.hip (context, options, scratch, the
-stream-ordered block cache behind hipdsp_malloc / hipdsp_free) and sos_plan.hip (plan mathematics, segment planner)
+stream-ordered block cache behind hipdsp_malloc / hipdsp_free), sos_plan.hip (plan mathematics, segment planner) and
+spec_host.hip (the spectrogram's frame count, window sum and FFT tables, each against its definition restated here)
 are compiled with g++ against a fake HIP runtime (tests/fakehip: host memory, streams and events as heap objects)
 and driven through the C ABI by a small program; any out-of-bounds access, leak or UB aborts it."""
 
@@ -13,9 +14,11 @@ DRIVER = r'''
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <cmath>
 #include <vector>
 #include "hip/hip_runtime.h"
 #include "hip_dsp.h"
+#include "common.h"
 size_t fake_hip_limit = 0, fake_hip_in_use = 0;
 int fake_hip_fail_event_create = 0;
 long fake_hip_waits = 0;
@@ -47,6 +50,28 @@ hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned)
 }
 #define CHECK(x) do { int rc_ = (x); if (rc_ != 0) { printf("line %d: rc %d: %s\n", __LINE__, rc_, hipdsp_last_error()); return 1; } } while (0)
 #define EXPECT(c) do { if (!(c)) { printf("line %d: %s\n", __LINE__, #c); return 1; } } while (0)
+// the table set of one nfft as plain loops: tw2 | tw3 | twn | window (R3 > 0) or tw2 | twn | window (R3 == 0)
+static std::vector<float> tables_by_definition(int nfft, int R1, int R2, int R3)
+{
+    const int M = nfft / 2;
+    std::vector<float> v;
+    auto cis = [&](double a) { v.push_back((float)cos(a)); v.push_back((float)sin(a)); };
+    if (R3 > 0) {
+        for (int t = 1; t < R2; t++) for (int k = 0; k < R1; k++) cis(-2.0 * M_PI * (double)(k * t) / (double)(R1 * R2));
+        for (int k = 0; k < R1 * R2; k++) cis(-2.0 * M_PI * (double)k / (double)M);
+    } else {
+        for (int t = 1; t < R2; t++) for (int k = 0; k < R1; k++) cis(-2.0 * M_PI * (double)(k * t) / (double)M);
+    }
+    for (int k = 0; k <= M / 2; k++) cis(-2.0 * M_PI * (double)k / (double)nfft);
+    for (int i = 0; i < nfft; i++) v.push_back((float)(0.5 - 0.5 * cos(2.0 * M_PI * (double)i / (double)nfft)));
+    return v;
+}
+// every set the dispatch of hipdsp_spectrogram and hd_fft_tables can ask for
+static const int TABLE_SETS[][4] = {
+    {256, 8, 4, 4}, {512, 8, 8, 4}, {1024, 8, 8, 8}, {2048, 16, 16, 4}, {4096, 16, 16, 8}, {8192, 16, 16, 16},
+    {16384, 16, 16, 32}, {32768, 16, 32, 32},
+    {8, 2, 2, 0}, {16, 4, 2, 0}, {32, 8, 2, 0}, {64, 8, 4, 0}, {128, 8, 8, 0}, {256, 16, 8, 0}, {512, 16, 16, 0},
+    {1024, 32, 16, 0}, {2048, 32, 32, 0}};
 int main()
 {
     // ---- plan mathematics and the segment planner over many inputs
@@ -77,9 +102,60 @@ int main()
         int64_t seg; int n;
         EXPECT(hipdsp_sos_segments_host(0, 16, 4, 0, 10, 1, 0, &seg, &n) == HIPDSP_ERR_INVALID);
     }
+    // ---- frames inside a trace: the number of k in [0, frames_out) with k * hop + nfft <= avail
+    for (int nfft : {8, 100, 256, 2048})
+        for (int hop : {1, nfft / 4, nfft / 2, nfft})
+            for (long long avail : {0LL, nfft - 1LL, (long long)nfft, nfft + hop - 1LL, (long long)nfft + hop, 5LL * nfft + 3})
+                for (long long frames_out : {0LL, 1LL, 3LL, 1000LL}) {
+                    long long count = 0;
+                    for (long long k = 0; k < frames_out; k++) count += (k * hop + nfft <= avail) ? 1 : 0;
+                    EXPECT(hd_frames_valid(frames_out, avail, nfft, hop) == count);
+                }
+    // ---- the window's sum of squares, bit for bit
+    for (int nfft : {8, 100, 524288}) {
+        double wss = 0.0;
+        for (int i = 0; i < nfft; i++) {
+            const double w = 0.5 - 0.5 * cos(2.0 * M_PI * (double)i / (double)nfft);
+            wss += w * w;
+        }
+        const double got = hd_hann_sumsq(nfft);
+        EXPECT(memcmp(&got, &wss, sizeof(wss)) == 0);
+    }
     // ---- context, options, scratch, block cache
     hipdsp_ctx *ctx = nullptr;
     CHECK(hipdsp_ctx_create(0, nullptr, &ctx));
+    // ---- FFT tables: refused on first use inside a capture (nothing allocated), then bit for bit the definition, then cached
+    {
+        void *cs = nullptr;
+        CHECK(hipdsp_stream_create(ctx, &cs));
+        CHECK(hipdsp_ctx_set_stream(ctx, cs));
+        for (const auto &t : TABLE_SETS) {
+            const float *dev = nullptr, *again = nullptr;
+            const size_t before = fake_hip_in_use;
+            ctx->stream->capturing = 1;
+            EXPECT(hd_fft_table_set(ctx, t[0], t[1], t[2], t[3], &dev) == HIPDSP_ERR_INVALID);
+            ctx->stream->capturing = 0;
+            EXPECT(dev == nullptr && fake_hip_in_use == before);
+            CHECK(hd_fft_table_set(ctx, t[0], t[1], t[2], t[3], &dev));
+            const std::vector<float> want = tables_by_definition(t[0], t[1], t[2], t[3]);
+            EXPECT(fake_hip_in_use == before + want.size() * sizeof(float));
+            EXPECT(memcmp(dev, want.data(), want.size() * sizeof(float)) == 0);
+            ctx->stream->capturing = 1;                             // a cached set is served inside a capture too
+            CHECK(hd_fft_table_set(ctx, t[0], t[1], t[2], t[3], &again));
+            ctx->stream->capturing = 0;
+            EXPECT(again == dev && fake_hip_in_use == before + want.size() * sizeof(float));
+        }
+        for (int i = 0; i < 4; i++) {                               // the fused sweeps' sets are the three-stage ones
+            const float *dev = nullptr, *same = nullptr;
+            CHECK(hd_fft_tables(ctx, TABLE_SETS[i][0], &dev));
+            CHECK(hd_fft_table_set(ctx, TABLE_SETS[i][0], TABLE_SETS[i][1], TABLE_SETS[i][2], TABLE_SETS[i][3], &same));
+            EXPECT(dev == same);
+        }
+        const float *none = nullptr;
+        EXPECT(hd_fft_tables(ctx, 4096, &none) == HIPDSP_ERR_UNSUPPORTED);
+        CHECK(hipdsp_ctx_set_stream(ctx, nullptr));
+        CHECK(hipdsp_stream_destroy(ctx, cs));
+    }
     EXPECT(hipdsp_ctx_set_option(ctx, "no_such_option", 1) == HIPDSP_ERR_INVALID);
     CHECK(hipdsp_ctx_set_option(ctx, "chain_reserve_cus", 8));
     EXPECT(hipdsp_ctx_set_option(ctx, "n_cus", 4) == HIPDSP_ERR_INVALID);    // fewer CUs than reserved: refused (ADVICE round 2)
@@ -180,6 +256,7 @@ def test_host_only_units_are_clean_under_asan_ubsan(tmp_path):
     subprocess.check_call(['g++', '-O1', '-g', '-std=c++17', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
                            '-I', os.path.join(ROOT, 'tests', 'fakehip'), '-I', os.path.join(ROOT, 'include'), '-I', csrc,
                            '-x', 'c++', str(src), os.path.join(csrc, 'ctx.hip'), os.path.join(csrc, 'sos_plan.hip'),
+                           os.path.join(csrc, 'spec_host.hip'),
                            '-o', str(exe)])
     env = dict(os.environ, ASAN_OPTIONS='detect_leaks=1', UBSAN_OPTIONS='print_stacktrace=1')
     r = subprocess.run([str(exe)], capture_output=True, text=True, env=env, timeout=300)
