@@ -23,21 +23,12 @@ struct hipdsp_ctx {
     int sos_waves_per_cu;  // experiments: resident waves per CU the IIR planner aims for
     int sos_waves_min;     // experiments: >= sos_waves_per_cu forces exactly that many waves per CU (sos.hip: plan_segments)
     int chain_pairs;       // most pairs of waves per CU the fused sweeps' planner uses (0 = 8; experiments)
-    int sos_debug;         // measurements only (results wrong): ablation bits of the envelope's backward sweep
-    int sos_single_wave_wg; // experiments (A/B): the envelope's backward sweep as single-wave workgroups, as in rounds 1-2
     int sos_prefetch;      // experiments: register prefetch of the next tile in the envelope sweeps
     int spec_no_half;      // experiments/tests: do not reuse the overlapped half frame
     int spec_fpw, spec_kernel;   // experiments (tools/), 0 = defaults
-    int spec_debug;        // measurements only (results wrong): ablation bits of spec_pack_kernel (spec_pack.h)
     int chain_debug;       // experiments: ablation bits of the fused forward kernel
     int chain_split_frames; // hipdsp_chain_forward writes only the even frames (hipdsp_chain_backward the odd ones)
     int chain_reserve_cus; // CUs hipdsp_chain_forward leaves without a workgroup (room for a co-resident RCCL kernel)
-    long long *sos_trace;  // diagnostics: device buffer (9 int64 per WAVE of the envelope's backward sweep = channels x segments
-                           // rows, hipdsp_chain... sizes unknown to the library: the tool sizes it from the planned grid)
-    long long sos_trace_rows;  // capacity of sos_trace in rows of 9 int64 (option "sos_trace_rows"; set it BEFORE "sos_trace")
-    int sos_fair;          // rotating issue priorities in the single-wave sweeps (sos.hip: rotate_issue_priority)
-    int sos_split;         // experiments (A/B): the envelope's backward sweep with compute and mover waves (envsplit.hip)
-    int sos_no_pin;        // experiments: scalar table loads left to hipcc's just-in-time placement (A/B of CASC_PIN_GROUPS)
     struct hd_pool *pool;  // stream-ordered cache of freed device blocks (ctx.hip)
     // Device-side fault report: four ints in pinned host memory that kernels can write
     // (word 0 = fault code, 1..3 = detail).  A kernel whose bounded wait runs out stores here instead of
@@ -61,7 +52,6 @@ int hd_seg_flags(hipdsp_ctx *ctx, size_t units, unsigned char **out);
 
 // fault codes a kernel may leave in hipdsp_ctx::fault_host[0]
 #define HD_FAULT_CHAIN_HANDOVER 1   // chain_fwd_kernel: a wave waited in vain for its partner's LDS flag
-#define HD_FAULT_SPLIT_HANDOVER 2   // env_bwd_split_kernel: the same between a compute wave and its mover
 
 // Reports (and clears) a fault word left by a kernel of this context: HIPDSP_ERR_HIP with a message,
 // HIPDSP_OK when there is none.  Called after every synchronisation of the context's stream and at

@@ -93,16 +93,10 @@ int hipdsp_ctx_create(int device, void *stream, hipdsp_ctx **out)
     ctx->force_generic_fft = 0;
     ctx->spec_fpw = ctx->spec_kernel = 0;
     ctx->chain_debug = 0;
-    ctx->sos_no_pin = 0;
-    ctx->sos_trace = nullptr;
-    ctx->sos_fair = 0;
     ctx->chain_reserve_cus = 0;
     ctx->chain_split_frames = 0;
     ctx->sos_waves_per_cu = 0;
     ctx->sos_waves_min = 0;
-    ctx->sos_trace_rows = 0;
-    ctx->sos_single_wave_wg = 0;
-    ctx->sos_debug = 0;
     ctx->chain_pairs = 0;
     ctx->spec_no_half = 0;
     ctx->pool = new hd_pool();
@@ -200,8 +194,6 @@ int hipdsp_ctx_set_option(hipdsp_ctx *ctx, const char *name, long long value)
         ctx->chain_pairs = (int)value;
         return HIPDSP_OK;
     }
-    if (strcmp(name, "sos_debug") == 0) { ctx->sos_debug = (int)value; return HIPDSP_OK; }
-    if (strcmp(name, "sos_single_wave_wg") == 0) { ctx->sos_single_wave_wg = value != 0; return HIPDSP_OK; }
     if (strcmp(name, "sos_prefetch") == 0) { ctx->sos_prefetch = value != 0; return HIPDSP_OK; }
     if (strcmp(name, "pool_limit_mb") == 0) {
         HD_REQUIRE(value >= 0, "pool_limit_mb must be >= 0");
@@ -217,26 +209,7 @@ int hipdsp_ctx_set_option(hipdsp_ctx *ctx, const char *name, long long value)
     }
     if (strcmp(name, "spec_no_half") == 0) { ctx->spec_no_half = value != 0; return HIPDSP_OK; }
     if (strcmp(name, "spec_kernel") == 0) { ctx->spec_kernel = (int)value; return HIPDSP_OK; }
-    if (strcmp(name, "spec_debug") == 0) { ctx->spec_debug = (int)value; return HIPDSP_OK; }
     if (strcmp(name, "chain_debug") == 0) { ctx->chain_debug = (int)value; return HIPDSP_OK; }
-    if (strcmp(name, "sos_no_pin") == 0) { ctx->sos_no_pin = value != 0; return HIPDSP_OK; }
-    if (strcmp(name, "sos_split") == 0) {
-#ifdef HIPDSP_WITH_ENVSPLIT
-        ctx->sos_split = value != 0;
-        return HIPDSP_OK;
-#else
-        if (value == 0) return HIPDSP_OK;
-        hipdsp_set_error("\"sos_split\": this library was built without envsplit.hip (make SPLIT=1)");
-        return HIPDSP_ERR_UNSUPPORTED;
-#endif
-    }
-    if (strcmp(name, "sos_fair") == 0) { ctx->sos_fair = value != 0; return HIPDSP_OK; }
-    if (strcmp(name, "sos_trace_rows") == 0) { ctx->sos_trace_rows = value; return HIPDSP_OK; }
-    if (strcmp(name, "sos_trace") == 0) {
-        HD_REQUIRE(value == 0 || ctx->sos_trace_rows > 0, "set \"sos_trace_rows\" (capacity of the buffer in rows of 9 int64) first");
-        ctx->sos_trace = reinterpret_cast<long long *>((uintptr_t)value);
-        return HIPDSP_OK;
-    }
     if (strcmp(name, "chain_split_frames") == 0) { ctx->chain_split_frames = value != 0; return HIPDSP_OK; }
     if (strcmp(name, "chain_reserve_cus") == 0) {
         HD_REQUIRE(value >= 0 && value < ctx->n_cus, "chain_reserve_cus %lld not in [0, %d)", value, ctx->n_cus);

@@ -482,27 +482,16 @@ int launch_env_fix(hipdsp_ctx *ctx, const SosPlanDev *edev, int SE, double *ckpt
 // G groups before using either and put the lane-0 branch of the state fold between fetch and use (264 SGPR spills,
 // 6.0-6.1 ms against 5.9); with CASC_CARRY_AFTER_F and the opaque `last` below it has 60 spills and 15 % fewer
 // instructions per tile: 8 % fewer cycles (SQ_BUSY_CYCLES, profiles/r03_bwd_regw_ab.log), 1-5 % less time free-running.
-template <int SE, bool PREFETCH, bool PIN = true, bool TRACE = false, int WPB_ = WPB, bool REGW = (SE <= 2)>
-__global__ __launch_bounds__(64 * WPB_, REGW ? 2 : 1) void env_bwd_kernel(const SosPlanDev *__restrict__ P0, BwdArgs a)
+template <int SE, bool PREFETCH, bool REGW = (SE <= 2)>
+__global__ __launch_bounds__(64 * WPB, REGW ? 2 : 1) void env_bwd_kernel(const SosPlanDev *__restrict__ P0, BwdArgs a)
 {
-    // TRACE (diagnostic build, option "sos_trace"): shader clocks per part of an iteration, summed per wave
-    long long tr_acc[6] = {0, 0, 0, 0, 0, 0};
-    long long tr_last = TRACE ? clock64() : 0;
-#define TRACE_AT(i)                                              \
-    do {                                                         \
-        if (TRACE) {                                             \
-            const long long t_ = clock64();                      \
-            tr_acc[(i)] += t_ - tr_last;                         \
-            tr_last = t_;                                        \
-        }                                                        \
-    } while (0)
     constexpr int DE = 2 * SE;
-    __shared__ float4 lds_all[WPB_][64 * 8];
+    __shared__ float4 lds_all[WPB][64 * 8];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     float4 *lds = lds_all[wave];
     float *ldsf = reinterpret_cast<float *>(lds);
     const int lane = threadIdx.x & 63;
-    const long long unit = (long long)blockIdx.x * WPB_ + wave;
+    const long long unit = (long long)blockIdx.x * WPB + wave;
     if (unit >= a.units) return;                    // (no workgroup barrier anywhere: a wave may leave)
     const int seg = (int)(unit % a.n_seg);
     const long long ch = unit / a.n_seg;
@@ -511,8 +500,6 @@ __global__ __launch_bounds__(64 * WPB_, REGW ? 2 : 1) void env_bwd_kernel(const 
     const double *ckpt = a.ckpt + ch * a.ckpt_pitch;
     const long long T = a.T;
     const int edge = a.edge;
-    const long long trace_t0 = a.trace ? wall_clock64() : 0;
-    const unsigned slot = wave_slot_of_simd();
 
     // reversed tile index rt = n_tiles-1 - (p / TILE): the wave owns rt in [rt_lo, rt_hi)
     const long long rt_lo = (long long)seg * a.seg_tiles;
@@ -551,9 +538,8 @@ __global__ __launch_bounds__(64 * WPB_, REGW ? 2 : 1) void env_bwd_kernel(const 
     v4f nx[8], nck[SE];
     bool pre = false;
     auto fetch = [&](long long tidx) {
-        const long long tsrc = (a.debug & 2) ? 0 : tidx;
 #pragma unroll
-        for (int k = 0; k < 8; k++) nx[k] = asm_load16(in + tsrc * TILE + 256 * k + 4 * lane);
+        for (int k = 0; k < 8; k++) nx[k] = asm_load16(in + tidx * TILE + 256 * k + 4 * lane);
 #pragma unroll
         for (int i = 0; i < SE; i++) nck[i] = asm_load16(ckpt + tidx * DE + 2 * i);
     };
@@ -579,7 +565,6 @@ __global__ __launch_bounds__(64 * WPB_, REGW ? 2 : 1) void env_bwd_kernel(const 
         const long long tidx = a.n_tiles - 1 - rt;
         const long long tile = tidx * TILE;
         if (tile + TILE <= a.skip) break;          // nothing below `skip` is kept
-        if (a.fair) rotate_issue_priority(slot);
         double cfw_[DE];
         // ---- trace tile -> LDS, rectified
         if (PREFETCH && pre) {
@@ -683,17 +668,15 @@ __global__ __launch_bounds__(64 * WPB_, REGW ? 2 : 1) void env_bwd_kernel(const 
             // and its first value in front of it (the tile's state, zi * that value, is in the tile states)
             (void)env_left_fill(ldsf, lane, (int)(a.env0 - tile), edge);
         }
-        TRACE_AT(0);                               // tile from the prefetch registers into LDS
         if (PREFETCH) {
             pre = rt + 1 < rt_hi && prefetchable(tidx - 1);
             fetch(pre ? tidx - 1 : top_full);
         }
-        TRACE_AT(1);                               // prefetch of the next tile issued
         // ---- forward cascade again, from the state that entered this tile
 #define CASC_S SE
 #define CASC_PLAN() PLAN_OF(P0)
 #define CASC_IN(v) (v)
-#define CASC_PIN_GROUPS PIN
+#define CASC_PIN_GROUPS true
       if constexpr (REGW) {
 #define CASC_CARRY_AFTER_F
         double w_[L];
@@ -707,7 +690,6 @@ __global__ __launch_bounds__(64 * WPB_, REGW ? 2 : 1) void env_bwd_kernel(const 
 #undef CASC_GAIN
 #undef CASC_CARRY
         WAVE_SYNC();
-        TRACE_AT(2);
         if (rt == 0) {
             int last = (int)(T + edge - 1 - tile);
             asm volatile("" : "+v"(last));              // or its 32 lane masks are hoisted out of the sweep into SGPRs
@@ -737,7 +719,6 @@ __global__ __launch_bounds__(64 * WPB_, REGW ? 2 : 1) void env_bwd_kernel(const 
 #undef CASC_GAIN
 #undef CASC_CARRY
         WAVE_SYNC();
-        TRACE_AT(2);
         if (rt == 0) {
             const int last = (int)(T + edge - 1 - tile);
             const float v0 = ldsf[lds_float_index(last)];
@@ -759,7 +740,6 @@ __global__ __launch_bounds__(64 * WPB_, REGW ? 2 : 1) void env_bwd_kernel(const 
 #undef CASC_PLAN
 #undef CASC_IN
         WAVE_SYNC();
-        TRACE_AT(3);                               // backward cascade
         if (rt >= rt_lo) {
             if (tile >= a.skip && tile + TILE <= T) {
                 // interior tile: exactly 8 vector stores (max(x, 0) as one instruction: fmaxf() costs a second one
@@ -767,12 +747,11 @@ __global__ __launch_bounds__(64 * WPB_, REGW ? 2 : 1) void env_bwd_kernel(const 
                 v4f rows[8];
                 tile_rows_from_lds(lds, lane, rows);
                 if (a.clamp) {
-                    const long long tdst = (a.debug & 1) ? a.skip : tile;
 #pragma unroll
                     for (int k = 0; k < 8; k++) {
                         const v4f v = rows[k];
                         f4u t; t.x = max_zero(v.x); t.y = max_zero(v.y); t.z = max_zero(v.z); t.w = max_zero(v.w);
-                        *reinterpret_cast<f4u *>(out + (tdst + 256 * k + 4 * lane - a.skip)) = t;
+                        *reinterpret_cast<f4u *>(out + (tile + 256 * k + 4 * lane - a.skip)) = t;
                     }
                 } else {
 #pragma unroll
@@ -782,7 +761,6 @@ __global__ __launch_bounds__(64 * WPB_, REGW ? 2 : 1) void env_bwd_kernel(const 
                         *reinterpret_cast<f4u *>(out + (tile + 256 * k + 4 * lane - a.skip)) = t;
                     }
                 }
-                TRACE_AT(4);                       // 8 stores issued
                 // the prefetch issued above is older than these 8 stores: all but 7 operations done
                 // means every load has landed (one less than 8, so a merged store could not make
                 // the wait too weak; tools/check_prefetch_isa.py re-checks the ISA)
@@ -802,18 +780,6 @@ __global__ __launch_bounds__(64 * WPB_, REGW ? 2 : 1) void env_bwd_kernel(const 
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // warm-up tile: no stores to count
         }
         WAVE_SYNC();
-        TRACE_AT(5);                               // wait for the prefetch
-    }
-#undef TRACE_AT
-    if (a.trace && lane == 0 && unit < a.trace_rows) { // tools/sweep_trace.py: do the waves of a SIMD progress alike?
-        unsigned hw;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        long long *tr = a.trace + 9 * unit;
-        tr[0] = trace_t0;
-        tr[1] = wall_clock64();
-        tr[2] = hw;
-#pragma unroll
-        for (int i = 0; i < 6; i++) tr[3 + i] = tr_acc[i];
     }
 }
 
@@ -1003,10 +969,6 @@ int launch_env_ckpt(hipdsp_ctx *ctx, const SosPlanDev *fdev, const SosPlanDev *e
     b.T = frames; b.skip = skip; b.n_tiles = ts.n_tiles; b.edge = edge;
     b.lead = gs.lead; b.env0 = gs.env0;
     b.rectify = rectify; b.clamp = clamp; b.gain = rectify ? gain : 1.0;
-    b.trace = ctx->sos_trace;
-    b.trace_rows = ctx->sos_trace_rows;
-    b.debug = ctx->sos_debug;
-    b.fair = ctx->sos_fair;
     const long long used_tiles = ts.n_tiles - skip / TILE;      // tiles below `skip` are never visited
     long long seg_len = 0;
     plan_segments(ctx, used_tiles * TILE, channels, warmE, &seg_len, &b.n_seg, 4, SE <= 2 ? 8 : 16);   // env_bwd_kernel: REGW
@@ -1016,25 +978,14 @@ int launch_env_ckpt(hipdsp_ctx *ctx, const SosPlanDev *fdev, const SosPlanDev *e
     long long blocks = (b.units + WPB - 1) / WPB;            // four waves per workgroup: one per SIMD of a CU
     HD_REQUIRE(blocks <= 0x7fffffffLL, "grid too large");
     dim3 grid((unsigned)blocks), block(64 * WPB);
-#ifdef HIPDSP_WITH_ENVSPLIT
-    if (ctx->sos_split && SE <= 2 && frames >= 4 * TILE) return hd_launch_env_bwd_split(ctx, edev, SE, b);   // (A/B: envsplit.hip, make SPLIT=1)
-#endif
-    if (ctx->sos_single_wave_wg) { grid = dim3((unsigned)b.units); block = dim3(64); }
-    if (ctx->sos_single_wave_wg && SE == 1 && ctx->sos_prefetch && frames >= 4 * TILE && !ctx->sos_trace && !ctx->sos_no_pin) {
-        hipLaunchKernelGGL((env_bwd_kernel<1, true, true, false, 1>), grid, block, 0, ctx->stream, edev, b);   // A/B
-        return hd_launch_status("env_bwd_kernel");
-    }
-    if (ctx->sos_single_wave_wg) { grid = dim3((unsigned)blocks); block = dim3(64 * WPB); }
+    const bool pf = ctx->sos_prefetch && frames >= 4 * TILE;
     switch (SE) {
     case 1:
-        if (ctx->sos_prefetch && frames >= 4 * TILE) {
-            if (ctx->sos_trace) hipLaunchKernelGGL((env_bwd_kernel<1, true, true, true>), grid, block, 0, ctx->stream, edev, b);
-            else if (ctx->sos_no_pin) hipLaunchKernelGGL((env_bwd_kernel<1, true, false>), grid, block, 0, ctx->stream, edev, b);
-            else hipLaunchKernelGGL((env_bwd_kernel<1, true>), grid, block, 0, ctx->stream, edev, b);
-        } else hipLaunchKernelGGL((env_bwd_kernel<1, false>), grid, block, 0, ctx->stream, edev, b);
+        if (pf) hipLaunchKernelGGL((env_bwd_kernel<1, true>), grid, block, 0, ctx->stream, edev, b);
+        else hipLaunchKernelGGL((env_bwd_kernel<1, false>), grid, block, 0, ctx->stream, edev, b);
         break;
     case 2:
-        if (ctx->sos_prefetch && frames >= 4 * TILE) hipLaunchKernelGGL((env_bwd_kernel<2, true>), grid, block, 0, ctx->stream, edev, b);
+        if (pf) hipLaunchKernelGGL((env_bwd_kernel<2, true>), grid, block, 0, ctx->stream, edev, b);
         else hipLaunchKernelGGL((env_bwd_kernel<2, false>), grid, block, 0, ctx->stream, edev, b);
         break;
     case 3: hipLaunchKernelGGL((env_bwd_kernel<3, false>), grid, block, 0, ctx->stream, edev, b); break;

@@ -42,7 +42,6 @@ struct FloodArgs {
 int hd_launch_env_fix(hipdsp_ctx *ctx, const SosPlanDev *edev, int SE, double *ckpt, long long ckpt_pitch, long long channels,
                       int n_seg, long long seg_len, long long n_tiles, const FloodArgs *flood, int first_seg = 0);
 
-// (not in the anonymous namespace: envsplit.hip's launcher takes it across translation units)
 struct BwdArgs {
     const float *in;         // the trace the envelope is taken of (before rectification)
     float *out;
@@ -55,11 +54,6 @@ struct BwdArgs {
     double gain;             // as in CkptArgs
     long long units;         // channels * n_seg (the grid is rounded up to whole workgroups)
     long long lead, env0;    // as in CkptArgs: the grid of the forward sweep that left the tile states (skip >= env0)
-    long long *trace;        // option "sos_trace": 9 words per wave (start, end in 100 MHz ticks, HW_ID, 6 clock sums)
-    long long trace_rows;    // rows of `trace` (option "sos_trace_rows"): waves beyond it do not report
-    int debug;               // measurements only, results wrong (option "sos_debug"): 1 = every interior tile is stored into
-                             // the channel's first tile (writes stay in L2), 2 = every prefetch reads the first tile
-    int fair;                // rotate_issue_priority() per tile (option "sos_fair", default off: no gain measured)
 };
 
 namespace {
@@ -277,20 +271,6 @@ __device__ __forceinline__ float asm_load4(const float *p)
     return r;
 }
 
-// Fair shares of a SIMD for persistent waves that do not talk to each other.  The issue arbiters serve the
-// OLDEST wave first: of four waves of one SIMD that walk equal segments, the one in slot 0 gets whatever it
-// asks for and ends after 55 % of the launch, the one in slot 3 after 95 % (tools/sweep_trace.py), and the
-// tail with a quarter of the waves cannot keep the HBM pipes full.  Called once per tile, this gives the
-// four slots four DIFFERENT priorities that rotate with the shader clock (the same clock for all waves of
-// the SIMD, so the priorities stay distinct): every wave spends a quarter of the time at each level.
-__device__ __forceinline__ void rotate_issue_priority(unsigned slot)
-{
-    const unsigned p = (slot + (unsigned)(__builtin_readcyclecounter() >> 14)) & 3u;
-    if (p == 0) __builtin_amdgcn_s_setprio(0);
-    else if (p == 1) __builtin_amdgcn_s_setprio(1);
-    else if (p == 2) __builtin_amdgcn_s_setprio(2);
-    else __builtin_amdgcn_s_setprio(3);
-}
 // max(x, 0) as a single instruction (result as fmaxf(x, 0.f))
 __device__ __forceinline__ float max_zero(float x)
 {
@@ -304,12 +284,6 @@ __device__ __forceinline__ void set_issue_priority(int p)     // (s_setprio take
     else if (p == 1) __builtin_amdgcn_s_setprio(1);
     else if (p == 2) __builtin_amdgcn_s_setprio(2);
     else __builtin_amdgcn_s_setprio(3);
-}
-__device__ __forceinline__ unsigned wave_slot_of_simd()
-{
-    unsigned hw;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID, 0, 4)" : "=s"(hw));
-    return hw;
 }
 
 // a forward sweep has parked the envelope's tile states in the context scratch: remember its grid for phase 2
@@ -445,6 +419,3 @@ void plan_segments_chain(const hipdsp_ctx *ctx, long long N, long long channels,
 }
 
 }  // namespace
-
-// defined in envsplit.hip: the backward sweep with compute and mover waves (context option "sos_split")
-int hd_launch_env_bwd_split(hipdsp_ctx *ctx, const SosPlanDev *edev, int SE, const BwdArgs &b);

@@ -55,10 +55,8 @@ template <int NFFT, int LPF, int R1, int R2, int R3, bool DB>
 __global__ __launch_bounds__(256, NFFT >= 1024 ? 2 : 3) void spec_pack_kernel(
     const float *__restrict__ x, long long x_pitch, long long frames, long long n_valid, long long frames_out,
     long long out_pitch, int hop, float scale, const float *__restrict__ tables, float *__restrict__ out,
-    float *__restrict__ db_out, int batches_per_wave, int debug)
+    float *__restrict__ db_out, int batches_per_wave)
 {
-    // debug (option "spec_debug", measurements only, results wrong): 1 = no global stores, 2 = no fetches, 4 = no transform
-
     constexpr int M = NFFT / 2, PPL = M / LPF, G = 64 / LPF, F = M + 1, MP = M + M / 16;
     constexpr bool THREE = R3 > 1;
     constexpr bool INLANE = R3 == 4 && PPL == 8 && (R1 * R2) % 32 == 0;    // two last-stage butterflies per lane: see the split step
@@ -134,7 +132,6 @@ __global__ __launch_bounds__(256, NFFT >= 1024 ? 2 : 3) void spec_pack_kernel(
     };
     auto refill = [&](long long need) {
         while (ring_end < need) {
-            if (debug & 2) { ring_end += CHUNK; continue; }
             if (!pend_ok) request(ring_end);
             const int rbase = (int)(ring_end & (RB - 1));      // 0 or CHUNK: no wrap inside a fetch
 #pragma unroll
@@ -238,11 +235,7 @@ __global__ __launch_bounds__(256, NFFT >= 1024 ? 2 : 3) void spec_pack_kernel(
             const v2f pw = (re * re + im * im) * hscale2;
             pk = pw.x; pm = pw.y;
         };
-        if (debug & 4) {
-#pragma unroll
-            for (int m = 0; m < PPL; m++) { sg[l + LPF * m] = v[m].x; }
-            if (l == 0) sg[M] = v[0].y;
-        } else if constexpr (INLANE) {
+        if constexpr (INLANE) {
             // nfft 256 (M = 128 = 8 x 4 x 4, sixteen lanes per frame; 512 = 8 x 8 x 4 with 32 lanes alike): the last stage's
             // butterfly j (j < NS3 = M / 4) produces the bins j + NS3 t, and the partner of bin k is bin M - k: butterfly j
             // pairs with butterfly NS3 - j.  Which butterflies a lane takes is only a matter of the LDS addresses it
@@ -355,8 +348,8 @@ __global__ __launch_bounds__(256, NFFT >= 1024 ? 2 : 3) void spec_pack_kernel(
         __builtin_amdgcn_wave_barrier();
         // ---- nfr * F consecutive floats of the channel's spectrogram
         {
-            float *o = oc + ((debug & 1) ? 0 : fb0 * (long long)F);    // (1: every batch lands on the channel's first frames)
-            float *od = DB ? dc + ((debug & 1) ? 0 : fb0 * (long long)F) : nullptr;
+            float *o = oc + fb0 * (long long)F;
+            float *od = DB ? dc + fb0 * (long long)F : nullptr;
             auto put4 = [&](int i) {
                 const float4 p = *reinterpret_cast<const float4 *>(stage + i);
                 f4p t; t.x = p.x; t.y = p.y; t.z = p.z; t.w = p.w;
@@ -416,6 +409,6 @@ int run_pack(const SpecJob &j)
     const dim3 grid((unsigned)bx, (unsigned)j.channels), block(256);
     const auto kernel = j.db_out ? spec_pack_kernel<NFFT, LPF, R1, R2, R3, true> : spec_pack_kernel<NFFT, LPF, R1, R2, R3, false>;
     hipLaunchKernelGGL(kernel, grid, block, 0, j.ctx->stream, j.x, j.x_pitch, j.frames, j.n_valid, j.frames_out, j.out_pitch,
-                       j.hop, j.scale, tables, j.out, j.db_out, (int)bpw, j.ctx->spec_debug);
+                       j.hop, j.scale, tables, j.out, j.db_out, (int)bpw);
     return hd_launch_status("spec_pack_kernel");
 }

@@ -73,12 +73,6 @@ int hipdsp_ctx_set_max_segments(hipdsp_ctx *ctx, int max_segments);
  *   "chain_reserve_cus"  CUs hipdsp_chain_forward plans no workgroup for (0): its 1024-thread workgroups want a
  *                        whole CU each, so a kernel that stays resident next to it (RCCL's all-gather in the
  *                        multi-GPU step) needs CUs of its own or a second round of workgroups forms
- *   "sos_no_pin"         non-zero: plan tables fetched by just-in-time scalar loads (A/B, tools/pin_ab.py)
- *   "sos_trace"          diagnostics: device address (0 = off) of 9 int64 per wave (= channel x segment) of the
- *                        envelope's backward sweep -- start and end of the wave in 100 MHz ticks, its HW_ID, 6 clock
- *                        sums (tools/sweep_trace.py); "sos_trace_rows" (set it first) is the buffer's capacity in such
- *                        rows, waves beyond it do not report
- *   "sos_fair"           0: the single-wave sweeps without rotating issue priorities (A/B)
  *   "force_generic_fft"  non-zero: every nfft takes the generic radix-2 / four-step kernels
  *   "spec_kernel"        cross-check paths (results equal within the parity bar): 0 = default per size, 2 = the kernel a
  *                        size's default replaced (two-stage FFT, workgroup per frame, four-step path through HBM), 3 = the
@@ -99,6 +93,9 @@ int hipdsp_ctx_set_max_segments(hipdsp_ctx *ctx, int max_segments);
  *                        by one stream-ordered memset before the call's kernels (never the tile states a forward sweep
  *                        parked for its backward sweep, and not while the stream is capturing).  Results must not
  *                        depend on it at all, not even in rounding: what a call reads from the scratch it has written
+ * Any other name is refused with HIPDSP_ERR_INVALID, the retired experiment switches of the envelope's backward sweep
+ * and of the short-window spectrogram kernel included ("sos_split", "sos_single_wave_wg", "sos_no_pin", "sos_trace",
+ * "sos_trace_rows", "sos_fair", "sos_debug", "spec_debug"; their verdicts: DESIGN.md, "Retired experiments").
  * Device-side faults: the waits between the waves of hipdsp_chain_forward's kernel are bounded; a wave
  * whose wait runs out writes a fault word owned by the context and ends the launch early.
  * hipdsp_ctx_synchronize, hipdsp_memcpy_d2h, hipdsp_event_elapsed_ms and the next

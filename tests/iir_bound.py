@@ -20,7 +20,7 @@ held to that:
   none of which a running recurrence has; each adds a small multiple of the same (float64 rounding x noise gain)
   term, and 16 leaves an order of magnitude for that.  Cases are chosen with q <= Q_CAP = 2^-6, so the whole
   allowance is at most a quarter of one float32 rounding (tests/test_iir_bound.py holds the case list to the cap).
-* The odd extensions need no term for a low-pass envelope: sos.hip, envsplit.hip, chain.hip and chain_fwd.h form the
+* The odd extensions need no term for a low-pass envelope: sos.hip, chain.hip and chain_fwd.h form the
   right one (and, where the envelope starts inside the trace, the left one) in float32, 2.f*r(T-1) - r(T-2-i), and
   test_iir_bound.py shows the float64 recurrence with those extensions inside the bound with the 16 replaced by 1.
 * Two float32 roundings that the reference does not have and that sit in the sweeps' tile loops are held to DERIVED

@@ -942,6 +942,35 @@ def test_scratch_fill_option():
         c.close()
 
 
+RETIRED_OPTIONS = ('sos_split', 'sos_single_wave_wg', 'sos_no_pin', 'sos_trace', 'sos_trace_rows', 'sos_fair', 'sos_debug',
+                   'spec_debug')
+
+
+def test_retired_options_are_refused_and_change_nothing():
+    """The experiment switches of rounds 2-4 are unknown names now: each is refused, none is silently accepted, and the
+    envelope behind the refusals has the bytes of the one in front of them."""
+    from audian_amd import hipdsp
+    sos, esos, rate, x = sweep_input()
+    c, plans = hipdsp.Context(0), {}
+    r = Run(c, plans)
+    try:
+        dx = r.upload(np.ascontiguousarray(x.T))
+
+        def envelope():
+            dy = r.fresh((3, T))
+            hipdsp.envelope(c, r.plan('env', esos), dx, T, dy, T, 3, T, 0)
+            return [dy.to_host()]
+
+        want = envelope()
+        for name in RETIRED_OPTIONS:
+            with pytest.raises(ValueError, match='unknown option'):
+                c.set_option(name, 1)
+        same_bytes(envelope(), want, 'hipdsp_envelope behind the refused options')
+        c.synchronize()
+    finally:
+        close(c, plans)
+
+
 def test_no_fill_is_recorded_into_a_capture():
     """While the stream is capturing, a request for the scratch records no fill: a graph captured around
     hipdsp_ctx_reserve with the option on, replayed between a forward sweep and its backward sweep, leaves the parked

@@ -161,7 +161,9 @@ int main()
     EXPECT(hipdsp_ctx_set_option(ctx, "n_cus", 4) == HIPDSP_ERR_INVALID);    // fewer CUs than reserved: refused (ADVICE round 2)
     CHECK(hipdsp_ctx_set_option(ctx, "n_cus", 9));
     CHECK(hipdsp_ctx_set_option(ctx, "n_cus", 256));
-    EXPECT(hipdsp_ctx_set_option(ctx, "sos_trace", 1234) == HIPDSP_ERR_INVALID);     // capacity first
+    for (const char *retired : {"sos_split", "sos_single_wave_wg", "sos_no_pin", "sos_trace", "sos_trace_rows", "sos_fair",
+                                "sos_debug", "spec_debug"})      // the retired experiments: unknown names, not ignored ones
+        EXPECT(hipdsp_ctx_set_option(ctx, retired, 1) == HIPDSP_ERR_INVALID);
     CHECK(hipdsp_ctx_reserve(ctx, 1 << 20));
     CHECK(hipdsp_ctx_reserve(ctx, 1 << 10));                       // never shrinks
     void *sa = nullptr, *sb = nullptr;

@@ -35,8 +35,7 @@ for seed in range(first, first + N):
             r = _np.random.default_rng(seed*131 + len(name))
             opts = {'sos_waves_per_cu': int(r.choice([4, 8, 12, 16])), 'sos_prefetch': int(r.integers(0, 2)),
                     'spec_kernel': int(r.choice([0, 0, 2, 3])), 'spec_no_half': int(r.integers(0, 2)),
-                    'spec_fpw': int(r.choice([0, 0, 1, 3, 16])), 'sos_fair': int(r.integers(0, 2)),
-                    'sos_no_pin': int(r.integers(0, 2)), 'chain_reserve_cus': int(r.choice([0, 0, 8, 100])),
+                    'spec_fpw': int(r.choice([0, 0, 1, 3, 16])), 'chain_reserve_cus': int(r.choice([0, 0, 8, 100])),
                     'force_generic_fft': int(r.integers(0, 8) == 0)}
             for k, v in opts.items():
                 _gh.ctx().set_option(k, v)
