@@ -59,6 +59,7 @@ _vp = ctypes.c_void_p
 _i64 = ctypes.c_int64
 _int = ctypes.c_int
 _dbl = ctypes.c_double
+_flt = ctypes.c_float
 _sz = ctypes.c_size_t
 _pp = ctypes.POINTER(ctypes.c_void_p)
 
@@ -143,6 +144,14 @@ _SIGNATURES = {
     'hipdsp_firplan_set_host': ([_vp, _vp, _vp, _int, _int, _vp], _int),
     'hipdsp_firplan_upload': ([_vp, _vp], _int),
     'hipdsp_fir_bank': ([_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _vp, _i64, _i64], _int),
+    'hipdsp_template_prepare_host': ([_vp, _int, _int, _int, _int, _vp, _vp, _vp], _int),
+    'hipdsp_tmplplan_create': ([_vp, _pp], _int),
+    'hipdsp_tmplplan_destroy': ([_vp, _vp], _int),
+    'hipdsp_tmplplan_set': ([_vp, _vp, _vp, _int, _int, _int, _int], _int),
+    'hipdsp_tmplplan_set_host': ([_vp, _vp, _vp, _int, _int, _int, _int], _int),
+    'hipdsp_tmplplan_upload': ([_vp, _vp], _int),
+    'hipdsp_template_match': ([_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _dbl, _dbl, _flt, _flt, _dbl, _vp,
+                               _i64, _i64], _int),
     'hipdsp_region_stats': ([_vp, _vp, _i64, _i64, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _int, _vp], _int),
     'hipdsp_detect_events': ([_vp, _vp, _i64, _i64, _i64, _i64, _vp, _dbl, _i64, _i64, _i64, _vp, _i64, _vp], _int),
     'hipdsp_find_peaks': ([_vp, _vp, _i64, _i64, _i64, _i64, _vp, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _i64, _i64, _vp, _i64, _vp, _i64,

@@ -302,6 +302,61 @@ class FirPlan(_Handle):
         lib.hipdsp_firplan_destroy(self.ctx.handle, self._h)
 
 
+class TmplPlan(_Handle):
+    """Device-resident taps of up to 16 spectrogram templates of one shape (Tt frames, Fb bins), raw or normalised
+    (hipdsp_tmplplan_* in hip_dsp.h)."""
+
+    def __init__(self, ctx, templates=None, normalize=True):
+        self.ctx = ctx
+        h = ctypes.c_void_p()
+        check(lib.hipdsp_tmplplan_create(ctx.handle, ctypes.byref(h)))
+        self._h = h
+        self.n_templates = self.rows = self.cols = 0
+        self.normalize = bool(normalize)
+        if templates is not None:
+            self.set(templates, normalize)
+
+    def _call(self, fn, templates, normalize):
+        t = _templates(templates)
+        check(fn(self.ctx.handle, self._h, ctypes.c_void_p(t.ctypes.data), t.shape[0], t.shape[1], t.shape[2],
+                 int(bool(normalize))))
+        self.n_templates, self.rows, self.cols = t.shape
+        self.normalize = bool(normalize)
+
+    def set(self, templates, normalize=True):
+        self._call(lib.hipdsp_tmplplan_set, templates, normalize)
+
+    def set_host(self, templates, normalize=True):
+        self._call(lib.hipdsp_tmplplan_set_host, templates, normalize)
+
+    def upload(self):
+        check(lib.hipdsp_tmplplan_upload(self.ctx.handle, self._h))
+
+    def _destroy(self):
+        lib.hipdsp_tmplplan_destroy(self.ctx.handle, self._h)
+
+
+def _templates(templates):
+    t = np.asarray(templates, dtype=np.float64)
+    if t.ndim == 2:
+        t = t[None]
+    if t.ndim != 3:
+        raise ValueError('templates must be shape (n_templates, frames, bins)')
+    return np.ascontiguousarray(t)
+
+
+def template_prepare(templates, normalize=True):
+    """The taps the matrix core multiplies by, float32 (K, Tt, Fb), their sums H0 and centred square sums Q, float64
+    (hipdsp_template_prepare_host: no context, no device)."""
+    t = _templates(templates)
+    taps = np.empty(t.shape, np.float32)
+    h0, q = np.empty(len(t)), np.empty(len(t))
+    check(lib.hipdsp_template_prepare_host(ctypes.c_void_p(t.ctypes.data), t.shape[0], t.shape[1], t.shape[2],
+                                           int(bool(normalize)), ctypes.c_void_p(taps.ctypes.data),
+                                           ctypes.c_void_p(h0.ctypes.data), ctypes.c_void_p(q.ctypes.data)))
+    return taps, h0, q
+
+
 class Comm(_Handle):
     """RCCL communicator behind the C ABI (hipdsp_comm_*): rank 0 calls
     `Comm.unique_id()` and ships the 128 bytes to the other ranks."""
@@ -639,6 +694,19 @@ def fir_bank(ctx, plan, x, x_pitch, channels, frames, first, step, n_out, out, r
     check(lib.hipdsp_fir_bank(ctx.handle, _plan(plan), _p(x), int(x_pitch), int(channels), int(frames), int(first),
                               int(step), int(n_out), int(bool(rectify)), _p(out), int(out_pitch),
                               int(out_kernel_pitch)))
+
+
+def template_match(ctx, plan, spec, spec_pitch, channels, frames, nfreq, k0, first, n_out, out, db=False, ref_power=1.0,
+                   min_power=1e-20, floor=-np.inf, pivot=0.0, min_std=0.0, out_pitch=0, out_template_pitch=0):
+    """out[k, c, i] = the score of template k of `plan` against the window of Tt frames that starts at frame first + i
+    of spec[c], bins [k0, k0 + Fb): the correlation coefficient (a normalised plan) or the plain sum of products; NaN
+    where the window leaves [0, frames) or, normalised, is flatter than min_std (hipdsp_template_match): float32
+    products on the matrix cores."""
+    _count('template_match')
+    check(lib.hipdsp_template_match(ctx.handle, _plan(plan), _p(spec), int(spec_pitch), int(channels), int(frames),
+                                    int(nfreq), int(k0), int(first), int(n_out), int(bool(db)), float(ref_power),
+                                    float(min_power), float(floor), float(pivot), float(min_std), _p(out),
+                                    int(out_pitch), int(out_template_pitch)))
 
 
 def region_stats(ctx, x, x_pitch, channels, frames, regions, out=None):

@@ -269,6 +269,93 @@ class TraceGraph(object):
                 for a, b in events.frames(c).tolist()]
         return self.region_contours(rows, spec_name, fmin, fmax, min_power, drop_db)
 
+    # ---- spectrogram template matching ----------------------------------------------------------
+    def cut_template(self, t0, t1, fmin, fmax, channel, spec_name='spectrogram', log=True, floor_db=-120.0, name='template'):
+        """The patch of the spectrogram `spec_name` between t0 and t1 seconds and fmin and fmax Hz (the bins of
+        band_bins()) of one channel as a templates.Template: in dB floored at `floor_db` with `log`, else the powers.
+        The buffers are moved as in detect_events; with a device mirror only the patch crosses to the host."""
+        from . import hipdsp
+        from .bufferedspectrogram import band_bins
+        from .templates import Template, host_values
+        spec = self[spec_name]
+        i0, i1 = self._event_frames(spec, t0, t1)
+        F = int(spec.shape[2])
+        k0, k1 = band_bins(fmin, fmax, spec.fresolution, F)
+        a, b = i0 - spec.offset, i1 - spec.offset
+        n = len(spec._buf())
+        if a < 0 or b > n:
+            raise IndexError('range outside the loaded buffer')
+        if b <= a or k1 <= k0:
+            raise ValueError('the template would be empty: no frame or no bin inside the range')
+        if not 0 <= int(channel) < spec.channels:
+            raise IndexError(f'channel {channel} of {spec.channels}')
+        if spec._mirror_valid(a, b):
+            patch = hipdsp.DeviceArray(spec.ctx, (b - a, k1 - k0), np.float32)
+            hipdsp.memcpy2d(spec.ctx, patch, 4*(k1 - k0), spec._dev.view(int(channel)*spec._pitch() + a*F + k0, (1,)),
+                            4*F, 4*(k1 - k0), b - a)
+            power = patch.to_host().astype(np.float64)
+            patch.free()
+        else:
+            power = np.asarray(spec.buffer[a:b, int(channel), k0:k1], dtype=np.float64)
+        return Template(host_values(power, log, floor_db if log else -np.inf), k0*spec.fresolution, spec.fresolution,
+                        spec.tresolution, log, floor_db, name)
+
+    def match_templates(self, templates, spec_name='spectrogram', t0=None, t1=None, normalize=True, min_std=0.1,
+                        pivot=None):
+        """The score rows of all `templates` on the spectrogram `spec_name` between t0 and t1 seconds (by default its
+        current buffer): the buffers are moved as in detect_events, then templates.template_scores.  Returns
+        (scores, i0): (K, channels, frames) float32 -- a device array when the spectrogram has a device mirror -- and
+        the absolute frame of column 0."""
+        from .templates import template_scores
+        spec = self[spec_name]
+        i0, i1 = self._event_frames(spec, t0, t1)
+        if i0 is None:
+            i0, i1 = spec.offset, spec.offset + len(spec._buf())
+        return template_scores(spec, templates, i0, i1, normalize, min_std, pivot), i0
+
+    def detect_calls(self, templates, min_r=0.5, spec_name='spectrogram', t0=None, t1=None, min_std=0.1, pivot=None):
+        """Spectrogram cross-correlation as a detector: the correlation rows of all `templates` (match_templates),
+        their peaks of at least `min_r` (hipdsp_find_peaks on the rows, which stay on the device; numpy on a host-only
+        graph), and per channel the windows [peak - Tt//2, peak - Tt//2 + Tt) of all templates, overlapping ones merged,
+        as an Events on the spectrogram's frame grid (rate = the spectrogram's) -- what analyze_events, event_contours,
+        event_cross_correlation and attribute_events take as it is.  Returns (events, best_template, best_score): per
+        channel, aligned with the events, the index of the template with the highest peak inside each call and that
+        score."""
+        from . import hipdsp
+        from .events import Events
+        from .peaks import host_find_peaks
+        templates = list(templates)
+        spec = self[spec_name]
+        scores, i0 = self.match_templates(templates, spec_name, t0, t1, True, min_std, pivot)
+        K, C, n = scores.shape
+        if isinstance(scores, hipdsp.DeviceArray):
+            found = hipdsp.find_peaks(spec.ctx, scores, n, K*C, 0, n, (float(min_r), np.inf, -np.inf, np.inf, -np.inf, np.inf)) \
+                if K*C > 0 and n > 0 else []
+            scores.free()
+        else:
+            found = [host_find_peaks(scores[k, c], height=(float(min_r), None)) for k in range(K) for c in range(C)]
+        pairs, best, best_r = [], [], []
+        for c in range(C):
+            rows = []
+            for k in range(K if found else 0):
+                pos, props = found[k*C + c]
+                Tt = templates[k].values.shape[0]
+                rows.extend((int(p) - Tt//2 + i0, int(p) - Tt//2 + i0 + Tt, float(h), k) for p, h in zip(pos, props[:, 0]))
+            rows.sort()
+            merged = []
+            for a, b, r, k in rows:
+                if merged and a < merged[-1][1]:
+                    last = merged[-1]
+                    last[1] = max(last[1], b)
+                    if r > last[2]:
+                        last[2], last[3] = r, k
+                else:
+                    merged.append([a, b, r, k])
+            pairs.append(np.array([m[:2] for m in merged], dtype=np.int64).reshape(-1, 2))
+            best.append(np.array([m[3] for m in merged], dtype=np.int64))
+            best_r.append(np.array([m[2] for m in merged], dtype=np.float64))
+        return Events(pairs, spec.rate, spec.name), best, best_r
+
     def attribute_events(self, events, trace_name=None, max_delay=0.001, channels=None, min_r=0.5, min_ratio=1.0):
         """event_cross_correlation followed by the attribution rule (xcorr.attribute_events, whose two thresholds are
         not calibrated on recordings): returns (own, sources, delays) -- the Events that are their own source, and per

@@ -682,6 +682,94 @@ int hipdsp_fir_bank(hipdsp_ctx *ctx, const hipdsp_firplan *plan, const float *x,
                     int64_t channels, int64_t frames, int64_t first, int64_t step, int64_t n_out, int rectify,
                     float *out, int64_t out_pitch, int64_t out_kernel_pitch);
 
+/* ---- spectrogram template matching ("interface for event detectors") ------- */
+
+/* Spectrogram cross-correlation: one example call, cut out of a spectrogram, is slid along the spectrogram of every
+ * channel; the score of a window is the correlation of the template with the patch under it.
+ *
+ * Values.  spec is the planar slab (channels, frames, nfreq) float32 every spectrogram entry point writes, spec_pitch
+ * elements between channels (0 = frames*nfreq).  Of every frame only the band of bins [k0, k0 + Fb) is read.  Per
+ * element P the value is  v = decibel(P, ref_power, min_power)  with db != 0 -- bit for bit hipdsp_decibel's value --
+ * and v = P without; then v = floor where v < floor (floor a float, -inf for none; a NaN stays NaN).
+ *
+ * Templates.  K templates of one common shape (Tt, Fb): Tt frames of Fb bins.  hipdsp_template_prepare_host prepares
+ * the taps on the host, needs no context and no device:
+ *   raw mode (normalize == 0)   g = float32(h);
+ *   normalised mode             g = float32((h - mean h) / ||h - mean h||), mean and norm in extended precision;
+ * for both  sum_out[k] = H0 = sum g  and  norm_out[k] = Q = sum (g - mean g)^2  of the ROUNDED taps, summed in
+ * extended precision in row-major order and rounded to float64 once.  templates is (n, rows, cols) float64, taps_out
+ * (n, rows, cols) float32.  A template with a non-finite value (or, raw, one that overflows float32) is
+ * HIPDSP_ERR_INVALID; in normalised mode so is a template of zero variance (all values equal).  1 <= n <= 16,
+ * 1 <= rows <= 256, 1 <= cols, rows*cols <= 65536: larger is HIPDSP_ERR_UNSUPPORTED, zero or negative
+ * HIPDSP_ERR_INVALID.
+ *
+ * Score of template k, channel c, window start t = first + i, with n = Tt*Fb and w[a, b] = v[c, t + a, k0 + b]:
+ *   raw         s = sum g[a, b] * w[a, b]
+ *   normalised  r = sum g[a, b] * (w[a, b] - mean w) / sqrt(Q * D),  D = sum (w - mean w)^2: the Pearson coefficient of
+ *               the rounded template and the patch (np.corrcoef(g.ravel(), w.ravel())[0, 1]), |r| <= 1
+ *   out[k*out_template_pitch + c*out_pitch + i],  i < n_out   (out_pitch 0 = n_out, out_template_pitch 0 =
+ *   channels*out_pitch: the pitch defaults of hipdsp_band_power).
+ * NaN in both modes where the window does not lie inside [0, frames): first may be negative and first + i + Tt may
+ * pass frames.  NaN in normalised mode where the window holds a NaN or an infinity, or where D <= n*min_std^2 -- a patch
+ * too flat to match: silence at the floor, the spectrogram's zero tail frames; min_std >= 0 is in v's unit.  In raw
+ * mode non-finite values follow IEEE arithmetic.  Only the band's bins are ever read: the zero padding of the matrix
+ * core's K dimension is zeros in the values as well as in the taps, a NaN in bin k0 + Fb cannot leak in.  A window
+ * clear of every non-finite element gives what it gives without that element; other channels are not affected.
+ *
+ * pivot is a float the caller chooses, near the level of the values (the template's mean, the noise floor): the matrix
+ * core sees float32(v - pivot), which keeps dB values near -90 from costing the float32 accumulation its bits.  The
+ * definition's result does not depend on pivot, only the bound below does.
+ *
+ * The plan.  hipdsp_tmplplan_* hold the prepared taps in device memory as hipdsp_firplan_* hold FIR taps, with the
+ * same capture rules: hipdsp_tmplplan_set is hipdsp_tmplplan_set_host (hipdsp_template_prepare_host, then the taps laid
+ * out in pinned host memory; no stream work) followed by hipdsp_tmplplan_upload (an async copy on the stream, which
+ * may be captured), so a captured hipGraph replays under new templates.  hipdsp_template_match reads the template
+ * count, the shape and the mode from the host side of the plan at call time (a captured call keeps those of capture
+ * time: replay it only under template sets of the same count, shape and mode), and returns HIPDSP_ERR_INVALID while
+ * they differ from what was last uploaded.  hipdsp_tmplplan_set_host waits for the last upload enqueued outside a
+ * capture before it rewrites the pinned block; a replayed graph's copy is not known to it, so the caller synchronises
+ * the stream between a replay and the next hipdsp_tmplplan_set_host.  Normalised or raw is a property of the plan.
+ *
+ * HIPDSP_ERR_INVALID: a NULL ctx or plan, NULL spec or out with work to do, a negative size or pitch, a band outside
+ * [0, nfreq], a plan set but not uploaded, spec and out overlapping, min_std < 0, a NaN floor or a non-finite pivot, a
+ * pitch too small for the sizes.  A refused call writes nothing.  n_out == 0 or channels == 0 writes nothing.  At most
+ * 65535 channels and 2^36 windows per call.
+ *
+ * Arithmetic.  The products run on the f32-input matrix core (v_mfma_f32_16x16x4_f32), 16 windows x 16 templates per
+ * instruction; all 16 columns are always computed, the mapping is chosen by (Tt, Fb) alone, never by K, and the n
+ * products of a window are added in one fixed order (chunks of the band, inside a chunk frame by frame, bins in
+ * fours).  Normalised: per frame and channel the band sums S1 = sum (v - pivot) and S2 = sum (v - pivot)^2 are taken
+ * in float64 (v - pivot is exact there), added per window over its Tt frames directly, D = S2 - S1^2/n, numerator
+ * G - (S1/n)*H0 with G the float32 accumulator, one rounding to float32 at the end (and a clamp to [-1, 1]).  Raw:
+ * float32(G + pivot*H0) in float64, G itself at pivot == 0.
+ * Accuracy, with u = 2^-24, m = n + 3, gamma = m*u/(1 - m*u), e = 2^-53, M = sum |g| * |float32(v - pivot)| over the
+ * window, S2 as above (exact), every element held to it:
+ *   raw         |out - s| <= gamma*M + 4*e*|pivot*H0| + (pivot != 0: u*|s|, the float32 store)
+ *               exact when taps, values and all partial sums are integers below 2^24 and pivot == 0;
+ *   normalised  |out - r| <= gamma*M/sqrt(Q*D) + (n + 4)*e*sqrt(S2/n)*|H0|/sqrt(Q*D) + (3*n + 6)*e*(S2/D)*|r|
+ *                            + (u + 8*e)*|r| + 2^-149
+ * (tests/template_match_definition.py derives it).  The mask D <= n*min_std^2 is exact except for windows with
+ * |D - n*min_std^2| <= (3*n + 6)*e*S2 + 4*e*n*min_std^2.
+ * Promises: no atomics, no context scratch, all scalars by value: one kernel node inside hipdsp_graph_begin/end; the
+ * same call gives the same bits twice; a 16-template call gives bit for bit what 16 one-template calls give; a
+ * channel's or window's value does not depend on the other channels, on first, on n_out, on the pitches or on the tile
+ * it falls in; nothing outside the requested rows is written; index arithmetic on the slab is 64-bit and rows start at
+ * any 4-byte address. */
+typedef struct hipdsp_tmplplan hipdsp_tmplplan;
+int hipdsp_template_prepare_host(const double *templates, int n, int rows, int cols, int normalize,
+                                 float *taps_out, double *sum_out, double *norm_out);
+int hipdsp_tmplplan_create(hipdsp_ctx *ctx, hipdsp_tmplplan **out);
+int hipdsp_tmplplan_destroy(hipdsp_ctx *ctx, hipdsp_tmplplan *plan);
+int hipdsp_tmplplan_set(hipdsp_ctx *ctx, hipdsp_tmplplan *plan, const double *host_templates, int n_templates,
+                        int rows, int cols, int normalize);
+int hipdsp_tmplplan_set_host(hipdsp_ctx *ctx, hipdsp_tmplplan *plan, const double *host_templates,
+                             int n_templates, int rows, int cols, int normalize);
+int hipdsp_tmplplan_upload(hipdsp_ctx *ctx, hipdsp_tmplplan *plan);
+int hipdsp_template_match(hipdsp_ctx *ctx, const hipdsp_tmplplan *plan, const float *spec, int64_t spec_pitch,
+                          int64_t channels, int64_t frames, int64_t nfreq, int64_t k0, int64_t first,
+                          int64_t n_out, int db, double ref_power, double min_power, float floor, float pivot,
+                          double min_std, float *out, int64_t out_pitch, int64_t out_template_pitch);
+
 /* ---- region analysis -------------------------------------------------------- */
 
 /* Statistics of selected regions, reduced on the device: what the reference computes after the user selects a region.

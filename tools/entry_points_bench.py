@@ -152,6 +152,22 @@ for b in builds:
         logs[b['name']].append(f'{"hipdsp_spectral_features over the PSD 2048/1024, full band, " + name:78s} {ms:8.3f} ms {nbytes/ms/1e6:7.0f} GB/s')
         if b is builds[-1]:
             print(logs[b['name']][-1], flush=True)
+# ---- hipdsp_template_match over the same PSD slab: 16 normalised templates of 32 frames x 128 bins on the dB values
+# (tools/template_match_bench.py has the other shapes, the raw mode and hipdsp_fir_bank at the same tap count)
+for b in builds:
+    h, ctx = b['h'], b['ctx']
+    if not hasattr(h.lib, 'hipdsp_template_match'):
+        continue
+    ds, out = b['buf']['ds'], b['buf']['db']
+    plan = h.TmplPlan(ctx, np.random.default_rng(7).uniform(-100.0, -40.0, (16, 32, 128)), True)
+    nbytes = 4.0*C*nd*(128 + 16)
+    ms = min(timed(b, lambda: h.template_match(ctx, plan, ds, 0, C, nd, F, 341, 0, nd, out, db=True, floor=-120.0, pivot=-90.0,
+                                               min_std=0.1), 5) for _ in range(rounds))
+    ctx.synchronize()
+    logs[b['name']].append(f'{"hipdsp_template_match over the PSD 2048/1024, 16 templates of 32 x 128, dB":78s} {ms:8.3f} ms {nbytes/ms/1e6:7.0f} GB/s')
+    if b is builds[-1]:
+        print(logs[b['name']][-1], flush=True)
+    plan.close()
 # ---- hipdsp_fir_bank: 16 kernels of 257 taps over the envelope, one frame per millisecond (tools/fir_bank_bench.py has the
 # other kernel lengths and steps)
 for b in builds:
