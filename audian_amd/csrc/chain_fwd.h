@@ -234,14 +234,46 @@ __device__ __forceinline__ void psd_frame_pivot(const v2f *w, float2 *fb, const 
         piv = (fabsf(c) <= 3.0e38f) ? c : p0;
         have_piv = true;
     }
-    const v2f pivot2 = {piv, piv};
+    // differences to the pivot `piv`, their sum and the sum of their squares
+    v2f sq;
+    auto sweep = [&]() {
+        const v2f pivot2 = {piv, piv};
+        acc = (v2f){0.f, 0.f};
+        sq = (v2f){0.f, 0.f};
 #pragma unroll
-    for (int t = 0; t < R1; t++) {
-        const v2f d = w[t] - pivot2;
-        v[t] = make_float2(d.x, d.y);
-        acc += d;
+        for (int t = 0; t < R1; t++) {
+            const v2f d = w[t] - pivot2;
+            v[t] = make_float2(d.x, d.y);
+            acc += d;
+            sq = __builtin_elementwise_fma(d, d, sq);
+        }
+    };
+    sweep();
+    float mean = gsum(acc.x + acc.y) * (1.0f / (float)NFFT);
+    // OWN PIVOT: a difference x - piv is rounded at ulp(x - piv), and where the level has moved since the frame the pivot
+    // came from (here: the frame two hops on, which does not overlap this one at all) that is far above the ulp of what
+    // the frame holds once its own mean is gone; no correction of the mean brings those bits back.  The carried pivot is
+    // as good as the frame's own while |mean| stays under the rms of what is left (spec_fast_kernel has the sum): every
+    // lane holds that against its 2 R1 samples, and where half the lanes of a frame find the mean above their rms
+    // (wave-uniform at LPF 64) the frame finds its own pivot in the two steps of a sequence's first frame -- from ITS first
+    // sample, so that a frame of equal samples comes out as exact zeros.
+    {
+        const bool far = 2.0f * (float)(2 * R1) * mean * mean > sq.x + sq.y;
+        const unsigned long long votes = __builtin_amdgcn_ballot_w64(far);
+        bool own = __builtin_popcountll(votes) >= 32;
+        if (LPF != 64) own = votes != 0;        // (several frames side by side: any lane, every frame of the wave)
+        if (own) {
+            float p0 = (LPF == 64) ? __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(w[0].x)))
+                                   : __shfl(w[0].x, (lane / LPF) * LPF, 64);
+            p0 = (fabsf(p0) <= 3.0e38f) ? p0 : 0.f;
+            piv = p0;
+            sweep();
+            const float c = p0 + gsum(acc.x + acc.y) * (1.0f / (float)NFFT);
+            piv = (fabsf(c) <= 3.0e38f) ? c : p0;
+            sweep();
+            mean = gsum(acc.x + acc.y) * (1.0f / (float)NFFT);
+        }
     }
-    const float mean = gsum(acc.x + acc.y) * (1.0f / (float)NFFT);
     {
         const float c = piv + mean;
         piv = (fabsf(c) <= 3.0e38f) ? c : piv;
@@ -251,14 +283,20 @@ __device__ __forceinline__ void psd_frame_pivot(const v2f *w, float2 *fb, const 
     // `mean` is good to 6e-8 of THEM, and the Hann window puts that error times nfft / 2 into bins 0 and 1.  The detrended
     // samples are summed once more; their mean m1 under the periodic Hann window is m1 nfft / 2 in bin 0, -m1 nfft / 4 in bin
     // 1 and nothing elsewhere, and the split step takes it out (spec_wgs.h, spec_pack.h and spec_fast_kernel do the same).
+    // (The rest is summed in float64 where the frame is the wave's: a float32 sum is good to eps times the LARGEST
+    // detrended sample, and the ringing behind a step of 1e6 levels that ended a sample before the frame -- 1e5 levels
+    // under window weights of 1e-6 -- left 7e-7 of it in bins 0 and 1 of a frame whose tone is 1: rho 2.07.  This path
+    // is the split sweep's alone; the stand-alone kernels keep float32.)
     v2f rest = {0.f, 0.f};
+    double rest64 = 0.0;
 #pragma unroll
     for (int t = 0; t < R1; t++) {
         const v2f q = as_v2f(v[t]) - mean2;
-        rest += q;
+        if (LPF == 64) rest64 += (double)q.x + (double)q.y;
+        else rest += q;
         v[t] = as_f2(q * as_v2f(win[l + LPF * t]));
     }
-    const float corr = 0.5f * gsum(rest.x + rest.y);
+    const float corr = LPF == 64 ? (float)(0.5 * wave_read_lane63(wave_prefix_sum(rest64))) : 0.5f * gsum(rest.x + rest.y);
     hook(0);                                   // mean and window
     psd_frame_core<NFFT, LPF, R1, R2, R3, DB, Hook>(v, corr, fb, tw2, tw3, twn, lane, scale, keep, out, hook);
 }

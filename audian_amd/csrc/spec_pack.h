@@ -169,7 +169,8 @@ __global__ __launch_bounds__(256, NFFT >= 1024 ? 2 : 3) void spec_pack_kernel(
             // part.  The pivot is the mean of the frame this lane group transformed in the batch before (`pvs`), not a
             // sample: a frame that starts on a pulse has that sample under a window weight of zero (chain.hip's psd_frame
             // has the case).  The run's first batch takes two steps: the batch's first sample (one LDS word, the same for
-            // every lane; zero if it is not finite) as the pivot of a rough mean, that mean as the pivot.
+            // every lane; zero if it is not finite) as the pivot of a rough mean, that mean as the pivot.  A carried pivot
+            // serves only where the level has not moved since: OWN PIVOT, below.
             // (Windows of up to 64 samples take the two steps in every batch: the mean of so few samples follows a single pulse
             // among them -- 1/8 of it at nfft 8 -- and would be a poor pivot for the frame that comes G frames later.)
             if (b == 0 || NFFT <= 64) {
@@ -187,18 +188,46 @@ __global__ __launch_bounds__(256, NFFT >= 1024 ? 2 : 3) void spec_pack_kernel(
                 const float c = p0 + group_sum<LPF>(a0.x + a0.y) * (1.0f / (float)NFFT);
                 pvs = (fabsf(c) <= 3.0e38f) ? c : p0;
             }
-            const v2f pivot2 = {pvs, pvs};
-            v2f acc = {0.f, 0.f};
+            // differences to the pivot `pvs`, their sum and (where the pivot is carried) the sum of their squares
+            constexpr bool CARRY = NFFT > 64;
+            v2f acc, sq;
+            auto sweep = [&]() {
+                const v2f pivot2 = {pvs, pvs};
+                acc = (v2f){0.f, 0.f};
+                sq = (v2f){0.f, 0.f};
 #pragma unroll
-            for (int u = 0; u < PPL / R1; u++)
+                for (int u = 0; u < PPL / R1; u++)
 #pragma unroll
-                for (int t = 0; t < R1; t++) {
-                    const int ri = (r0 + 2 * (LPF * u + t * (M / R1))) & (RB - 1);
-                    const v2f e = (v2f){ring[ri], ring[ri + 1]} - pivot2;
-                    v[u * R1 + t] = as_f2(e);
-                    acc += e;
+                    for (int t = 0; t < R1; t++) {
+                        const int ri = (r0 + 2 * (LPF * u + t * (M / R1))) & (RB - 1);
+                        const v2f e = (v2f){ring[ri], ring[ri + 1]} - pivot2;
+                        v[u * R1 + t] = as_f2(e);
+                        acc += e;
+                        if (CARRY) sq = __builtin_elementwise_fma(e, e, sq);
+                    }
+            };
+            sweep();
+            float mean = group_sum<LPF>(acc.x + acc.y) * (1.0f / (float)NFFT);
+            // OWN PIVOT: the carried pivot is G frames old, and a difference x - pvs is rounded at ulp(x - pvs): where the
+            // level has moved since (a fall back to the baseline most of all: small samples, a large pivot) that is far above
+            // the ulp of what the frame holds, and no correction of the mean brings those bits back.  The carried pivot is as
+            // good as the frame's own while |mean| stays under the rms of what is left (spec_fast_kernel has the sum): every
+            // lane holds that against its 2 PPL samples, and where any lane finds the mean above its rms every frame of the
+            // batch (wave-uniform) finds its own pivot from the ring, in the two steps of a run's first batch -- from ITS first
+            // sample, so that a frame of equal samples (silence behind sound) comes out as exact zeros.
+            if (CARRY) {
+                const bool far = 2.0f * (float)(2 * PPL) * mean * mean > sq.x + sq.y;
+                if (__builtin_amdgcn_ballot_w64(far) != 0) {
+                    float p0 = ring[(r0 - 2 * l) & (RB - 1)];
+                    p0 = (fabsf(p0) <= 3.0e38f) ? p0 : 0.f;
+                    pvs = p0;
+                    sweep();
+                    const float c = p0 + group_sum<LPF>(acc.x + acc.y) * (1.0f / (float)NFFT);
+                    pvs = (fabsf(c) <= 3.0e38f) ? c : p0;
+                    sweep();
+                    mean = group_sum<LPF>(acc.x + acc.y) * (1.0f / (float)NFFT);
                 }
-            const float mean = group_sum<LPF>(acc.x + acc.y) * (1.0f / (float)NFFT);
+            }
             const v2f mean2 = {mean, mean};
             {
                 const float c = pvs + mean;                          // the next batch's pivot (a NaN or Inf in this frame: unchanged)

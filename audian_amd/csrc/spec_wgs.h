@@ -50,7 +50,7 @@ __global__ __launch_bounds__(LPF, OCC) void spec_wgs_kernel(
     constexpr bool PIPE = PPL <= 16;
     constexpr bool KEEPW = PPL <= 16 && LPF >= 256;     // (nfft 8192; at 4096 the 32 registers are not there: spills)
     __shared__ __attribute__((aligned(16))) float2 smem[TW2 + TW3 + MP];
-    __shared__ float red[NW], red2[NW];
+    __shared__ float red[NW], red2[NW], redq[NW];
     const float2 *tw2 = smem, *tw3 = smem + TW2;
     float2 *fb = smem + TW2 + TW3;                     // (16-byte aligned: TW2 + TW3 is even)
     static_assert((TW2 + TW3) % 2 == 0, "frame buffer alignment");
@@ -87,15 +87,24 @@ __global__ __launch_bounds__(LPF, OCC) void spec_wgs_kernel(
     // frame finds its own in two steps (the run's first sample -- zero if that is not finite -- as the pivot of a rough
     // mean): a sample alone can be a pulse a thousand times the baseline under a window weight of zero (chain.hip's
     // psd_frame has that case).  A half that is kept for the next frame stays a difference to the pivot it was fetched
-    // under; the bookkeeping is two scalars (`pivot`, `delta`) and a per-half mean at the window.
+    // under; the bookkeeping is two scalars (`pivot`, `delta`) and a per-half mean at the window.  A carried pivot is only
+    // as good as the level is steady: a frame whose differences stand far off their own mean finds its own pivot (OWN
+    // PIVOT, below).
     float p0 = (nv > 0) ? xc[fbeg * (long long)hop] : 0.f;
     p0 = (fabsf(p0) <= 3.0e38f) ? p0 : 0.f;
     float pivot = p0, delta = 0.f;
     // the frame, as differences to the pivot, into LDS from (keep | nx); leaves the upper half in `keep` (differences as
-    // well: a sample meets the pivot once); returns the thread's share of the sum of the differences
+    // well: a sample meets the pivot once); returns the thread's share of the sum of the differences and (`sqs`) of the sum
+    // of their squares
+    float sqs = 0.f;
     auto put_raw = [&]() -> float {
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-        auto add = [&](float4 v) { acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w; };
+        v2f sq = {0.f, 0.f};
+        auto add = [&](float4 v) {
+            acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+            sq = __builtin_elementwise_fma((v2f){v.x, v.y}, (v2f){v.x, v.y}, sq);
+            sq = __builtin_elementwise_fma((v2f){v.z, v.w}, (v2f){v.z, v.w}, sq);
+        };
         auto rel = [&](float4 v) { return make_float4(v.x - pivot, v.y - pivot, v.z - pivot, v.w - pivot); };
         if (HALF) {
 #pragma unroll
@@ -110,11 +119,17 @@ __global__ __launch_bounds__(LPF, OCC) void spec_wgs_kernel(
 #pragma unroll
             for (int j = 0; j < NQ; j++) { const float4 d = rel(nx[j]); raw4[l + LPF * j] = d; add(d); }
         }
+        sqs = sq.x + sq.y;
         return (acc.x + acc.y) + (acc.z + acc.w);
     };
     auto post_sum = [&](float s) {
         s = wave_sum(s);
         if (lane == 0) red[wave] = s;
+    };
+    auto post_sums = [&](float s) {                   // ... and the squares put_raw() has just summed
+        post_sum(s);
+        const float q = wave_sum(sqs);
+        if (lane == 0) redq[wave] = q;
     };
 
     // periodic Hann 0.5 - 0.5 cos(2 pi i / nfft) at i = 2n, 2n + 1, n = n0 + t M / R1, n0 = l + LPF u: the angle of input t is
@@ -130,7 +145,18 @@ __global__ __launch_bounds__(LPF, OCC) void spec_wgs_kernel(
         for (int t = 0; t < R1; t++) {
             constexpr int STEP = 64 / R1;
             const float ct = wgs_cos64(STEP * t), st = wgs_sin64(STEP * t);
-            w[t] = make_float2(0.5f - 0.5f * (c0 * ct - s0 * st), 0.5f - 0.5f * (c1 * ct - s1 * st));
+            const float cx = c0 * ct - s0 * st, cy = c1 * ct - s1 * st;
+            if (t == 0 || t == R1 - 1) {
+                // The frame's two ends (within 1 / R1 of a turn of the window's zeros): 0.5 - 0.5 cos cancels there and
+                // leaves 3e-8 of absolute error on weights down to 1.5e-7 -- times a sample that stands S levels off the
+                // rest of the frame (the last one before a fall), spread over every bin: rho 6.8 behind S = 1e4 at nfft
+                // 8192.  (1 - cos) = sin^2 / (1 + cos) has no cancellation: the weight's error is sin times the sine's.
+                const float sx = s0 * ct + c0 * st, sy = s1 * ct + c1 * st;
+                w[t] = make_float2(0.5f * sx * sx * __builtin_amdgcn_rcpf(1.0f + cx),
+                                   0.5f * sy * sy * __builtin_amdgcn_rcpf(1.0f + cy));
+            } else {
+                w[t] = make_float2(0.5f - 0.5f * cx, 0.5f - 0.5f * cy);
+            }
         }
     };
     // KEEPW: where the registers allow (16 points per thread), the thread's window values stay in registers for the whole run
@@ -175,7 +201,7 @@ __global__ __launch_bounds__(LPF, OCC) void spec_wgs_kernel(
                     keep[j] = make_float4(keep[j].x - pivot, keep[j].y - pivot, keep[j].z - pivot, keep[j].w - pivot);
             }
         }
-        post_sum(put_raw());
+        post_sums(put_raw());
         if (PIPE && nv > 1) fetch(fbeg + 1);
         __syncthreads();                               // B0
         for (int it = 0; it < nv; it++) {
@@ -185,7 +211,62 @@ __global__ __launch_bounds__(LPF, OCC) void spec_wgs_kernel(
             for (int w = 0; w < NW; w++) total += red[w];
             // the halves of the frame in LDS are differences to the pivots in force when they were fetched: the upper half's
             // is `pivot`, the lower half's `pivot - delta`
-            const float mean = total * (1.0f / (float)NFFT) - 0.5f * delta;      // of (sample - pivot)
+            float mean = total * (1.0f / (float)NFFT) - 0.5f * delta;            // of (sample - pivot)
+            // OWN PIVOT: the differences in LDS were rounded at THEIR ulp, and where the level has moved since the pivot was
+            // taken -- a fall back to the baseline most of all: small samples, a large pivot -- that is far above the ulp of
+            // what the frame holds once its own mean is gone; no correction of the mean brings those bits back.  The halves
+            // stand off the frame's mean by `mean + delta` and `mean`; the carried pivot is as good as the frame's own while
+            // those offsets stay under the rms of what is left: n / 2 (lo^2 + hi^2) <= sum d^2 - n / 2 (lo^2 + hi^2)
+            // (spec_fast_kernel has the sum; the squares are summed next to the differences in put_raw()).  Otherwise
+            // (workgroup-uniform: everything here comes out of LDS) the frame is fetched again and finds its own pivot in
+            // the two steps of a run's first frame -- from ITS first sample, so that a frame of equal samples (silence behind
+            // sound) comes out as exact zeros.
+            {
+                float totq = 0.f;
+#pragma unroll
+                for (int w = 0; w < NW; w++) totq += redq[w];
+                const float lo = mean + delta;
+                if ((float)NFFT * (lo * lo + mean * mean) > totq) {
+                    __syncthreads();                   // (red[] has been read)
+                    const float *segf = xc + frame * (long long)hop;
+                    float q0 = segf[0];
+                    q0 = (fabsf(q0) <= 3.0e38f) ? q0 : 0.f;
+                    // (rare: rolled loops, a piece at a time -- the registers of the frame in flight stay where they are)
+                    float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 1
+                    for (int j = 0; j < NQ; j++) {
+                        const f4q t = *reinterpret_cast<const f4q *>(segf + 4 * (l + LPF * j));
+                        a0.x += t.x - q0; a0.y += t.y - q0; a0.z += t.z - q0; a0.w += t.w - q0;
+                    }
+                    post_sum((a0.x + a0.y) + (a0.z + a0.w));
+                    __syncthreads();
+                    float total0 = 0.f;
+#pragma unroll
+                    for (int w = 0; w < NW; w++) total0 += red[w];
+                    const float c = q0 + total0 * (1.0f / (float)NFFT);
+                    pivot = (fabsf(c) <= 3.0e38f) ? c : q0;
+                    delta = 0.f;
+                    __syncthreads();                   // (red[] is written again)
+                    float4 a1 = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 1
+                    for (int j = 0; j < NQ; j++) {
+                        const f4q t = *reinterpret_cast<const f4q *>(segf + 4 * (l + LPF * j));
+                        const float4 d = make_float4(t.x - pivot, t.y - pivot, t.z - pivot, t.w - pivot);
+                        raw4[l + LPF * j] = d;
+                        a1.x += d.x; a1.y += d.y; a1.z += d.z; a1.w += d.w;
+                    }
+                    post_sum((a1.x + a1.y) + (a1.z + a1.w));
+                    __syncthreads();
+                    if (HALF) {                        // the kept half: this thread's own pieces, back out of LDS
+#pragma unroll
+                        for (int j = 0; j < (HALF ? NQ / 2 : 0); j++) keep[j] = raw4[l + LPF * (j + NQ / 2)];
+                    }
+                    total = 0.f;
+#pragma unroll
+                    for (int w = 0; w < NW; w++) total += red[w];
+                    mean = total * (1.0f / (float)NFFT);
+                }
+            }
             // (an always-zero offset the compiler cannot see through: the window and the split twiddles do not depend on
             // the frame, and left alone hipcc computes them once, in front of the loop -- 96 registers that then live
             // through every frame)
@@ -318,7 +399,7 @@ __global__ __launch_bounds__(LPF, OCC) void spec_wgs_kernel(
                 }
                 delta = HALF ? dl : 0.f;
                 pivot = pn;
-                post_sum(put_raw());
+                post_sums(put_raw());
                 if (PIPE && it + 2 < nv) fetch(frame + 2);
             }
             if (PIPE) {

@@ -187,9 +187,9 @@ __global__ __launch_bounds__(64 * WAVES, (NFFT <= 2048 ? (DB ? 2 : 3) : 1) * WAV
         float *o = oc + frame * (long long)F;
         float *od = DB ? dc + frame * (long long)F : nullptr;
         float2 v[PPL];
-        v2f acc = {0.f, 0.f};                             // even and odd samples side by side (v_pk_add_f32)
         // the frame mean relative to a PIVOT, the mean of the frame this lane group transformed before (`pvs`; the run's
-        // first frame: the two steps in front of the first call) -- chain.hip's psd_frame has the two cases that ask for it
+        // first frame: the two steps in front of the first call; a frame behind a move of the level: OWN PIVOT, below) --
+        // chain.hip's psd_frame has the two cases that ask for it
         auto gsum = [&](float sum) {
             if (LPF == 64) return wave_sum(sum);
 #pragma unroll
@@ -217,20 +217,52 @@ __global__ __launch_bounds__(64 * WAVES, (NFFT <= 2048 ? (DB ? 2 : 3) : 1) * WAV
             const float c = pvs + gsum(a0.x + a0.y) * (1.0f / (float)NFFT);
             pvs = (fabsf(c) <= 3.0e38f) ? c : pvs;
         }
-        const v2f pivot2 = {pvs, pvs};
+        constexpr bool CORR = !TWOSTEP;
+        // differences to the pivot `pvs`, their sum and (CORR) the sum of their squares, from the raw registers
+        v2f acc, sq;
+        auto sweep = [&]() {
+            const v2f pivot2 = {pvs, pvs};
+            acc = (v2f){0.f, 0.f};
+            sq = (v2f){0.f, 0.f};
 #pragma unroll
-        for (int u = 0; u < PPL / R1; u++)
+            for (int u = 0; u < PPL / R1; u++)
 #pragma unroll
-            for (int t = 0; t < R1; t++) {
-                v2f *const qs[4] = {qa, qb, qc, qd};
-                v2f &r = qs[t / R1Q][u * R1Q + t % R1Q];
-                asm volatile("" : "+v"(r));               // not before the counted wait
-                const v2f d = r - pivot2;
-                v[u * R1 + t] = make_float2(d.x, d.y);
-                acc += d;
+                for (int t = 0; t < R1; t++) {
+                    v2f *const qs[4] = {qa, qb, qc, qd};
+                    v2f &r = qs[t / R1Q][u * R1Q + t % R1Q];
+                    asm volatile("" : "+v"(r));           // not before the counted wait
+                    const v2f d = r - pivot2;
+                    v[u * R1 + t] = make_float2(d.x, d.y);
+                    acc += d;
+                    if (CORR) sq = __builtin_elementwise_fma(d, d, sq);
+                }
+        };
+        sweep();
+        float mean = gsum(acc.x + acc.y) * (1.0f / (float)NFFT);
+        // OWN PIVOT (the variants with register reuse, whose pivot is the mean of the frame before): a difference x - pvs
+        // is rounded at ulp(x - pvs), and where the level has moved since the frame before -- a fall back to the baseline
+        // behind a stimulus artefact most of all: small samples, a large pivot -- that is far above the ulp of what the frame
+        // holds once its own mean is gone; no correction of the mean brings those bits back.  The rounding errors are
+        // (eps / 2) |d|, their norm against the detrended frame's is sqrt(1 + n mean^2 / sum q^2): the carried pivot is as good
+        // as the frame's own as long as |mean| stays under the rms of what is left, mean^2 n <= sum d^2 - n mean^2.  Every
+        // lane holds that against ITS 2 PPL samples (one fma per pair next to the sum, no second reduction), and where
+        // half the lanes find the mean above their rms (wave-uniform) the frame finds its own pivot from its raw
+        // registers, in the two steps of a run's first frame: its first sample, the rough mean relative to that.  (A
+        // frame of equal samples -- silence behind sound -- comes out as exact zeros that way; zero-mean audio behind any
+        // small pivot, and an offset that drifts, never get here.)
+        if (CORR) {
+            const bool far = 2.0f * (float)(2 * PPL) * mean * mean > sq.x + sq.y;
+            if (__builtin_popcountll(__builtin_amdgcn_ballot_w64(far)) >= 32) {
+                float p0 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(qa[0].x)));
+                p0 = (fabsf(p0) <= 3.0e38f) ? p0 : 0.f;
+                pvs = p0;
+                sweep();
+                const float c = p0 + gsum(acc.x + acc.y) * (1.0f / (float)NFFT);
+                pvs = (fabsf(c) <= 3.0e38f) ? c : p0;
+                sweep();
+                mean = gsum(acc.x + acc.y) * (1.0f / (float)NFFT);
             }
-        const float s = gsum(acc.x + acc.y);
-        const float mean = s * (1.0f / (float)NFFT);
+        }
         const v2f mean2 = {mean, mean};
         {
             const float c = pvs + mean;                   // the next frame's pivot (a NaN or Inf in this frame: unchanged)
@@ -241,7 +273,6 @@ __global__ __launch_bounds__(64 * WAVES, (NFFT <= 2048 ? (DB ? 2 : 3) : 1) * WAV
         // of THEM, and the Hann window puts that error times nfft / 2 into bins 0 and 1 (9e-5 of a flat frame's peak for a
         // step of 1000 sigma at 2048 / 1024).  The detrended samples are summed once more; their mean m1 under the window
         // is m1 nfft / 2 in bin 0, -m1 nfft / 4 in bin 1 and nothing elsewhere: the split step removes it.
-        constexpr bool CORR = !TWOSTEP;
         v2f rest = {0.f, 0.f};
 #pragma unroll
         for (int u = 0; u < PPL / R1; u++)

@@ -12,7 +12,8 @@ with eps = 2^-23, L = log2(nfft), r = rms_k a_k.  A bin under the float32 floor 
 that floor only, so no dB threshold needs picking.  (The floor is L r, not sqrt(L) r: see floor_growth.)  The
 direct DFT (non powers of two) sums nfft fmaf terms one after another: there sqrt(L) and L become sqrt(nfft).  Frames whose reference is all zero must
 be exactly zero.  tests/test_spectral_bound.py calibrates the bound on the CPU: a faithful float32 emulation
-passes with margin, injected defects (twiddles, window, edge bins, detrend) fail.
+passes with margin, injected defects (twiddles, window, edge bins, detrend, a pivot carried over from an earlier frame)
+fail.  FAMILIES are stationary; NONSTATIONARY move the level between frames (nonstationary()).
 """
 
 import numpy as np
@@ -163,3 +164,73 @@ def family(name, n, nfft, rate=48000.0, seed=0, levels=LEVELS):
             raise ValueError(name)
         x[:, c] = levels[c]*s
     return x.astype(np.float32)
+
+
+# ---- non-stationary families: the 'tones' base with an event in the level ------------------------------------
+
+NONSTATIONARY = ('fall', 'rise', 'staircase', 'burst', 'silence', 'pulses', 'transient')
+STEPS = (1e2, 1e4, 1e6)                    # S: the size of an event in units of the level (1e6: full scale / 24-bit LSB)
+PLACES = ('border', 'middle', 'before')    # the event sample: a frame border, a frame's middle, one sample before a border
+
+
+def event_sample(frame, nfft, hop, place):
+    return {'border': frame*hop, 'middle': frame*hop + nfft//2, 'before': frame*hop - 1}[place]
+
+
+def nonstationary(name, n, nfft, hop, rate=48000.0, seed=0, levels=LEVELS, S=1e4, place='border', frame=None,
+                  floor=0.0):
+    """A non-stationary test signal of `n` samples for windows of `nfft` every `hop`, float32 (n, len(levels)): the
+    'tones' base (120 dB inside a frame) at each channel's level, with an event at the sample `place` puts into
+    frame `frame` (default: the middle one of the frames that fit):
+
+    fall       raised by S times the level until the event sample, the baseline from there
+    rise       the baseline first, raised by S from the event sample
+    staircase  rises and falls of different sizes (S times 1, .25, .75, .1, .5, .05 ...) every third frame (every
+               frame where fewer than seven fit), the last one back to the baseline; `place` moves them all
+    burst      the base times 1e6 for three hops from the event sample: 120 dB between neighbours, no offset
+    silence    exact zeros over three whole frames from `frame` (one where fewer than seven fit) and over the
+               last frame; with `floor`, Gaussian noise at `floor` times the level in their place (see below)
+    pulses     a pulse of 1e3 levels on every frame's first sample (channel 0) / on the sample before it (channel 1)
+    transient  S exp(-t/tau) times the level added from the event sample, tau two hops: a filter's transient
+
+    `floor` is for traces that pass an IIR filter on their way to the transform.  Behind exact zeros the filter's
+    output decays through every magnitude down to the smallest float32, and the frames it crosses on the way have
+    reference powers under 1e-38: no float32 PSD holds them (they come out as denormals or zeros), which says
+    nothing about the transform.  A floor of 1e-9 levels keeps such frames 180 dB down and representable."""
+    i = NONSTATIONARY.index(name)
+    rng = np.random.default_rng([seed, i + len(FAMILIES), n, nfft])
+    t = np.arange(n, dtype=np.float64)
+    nseg = (n - nfft)//hop + 1
+    frame = nseg//2 if frame is None else frame
+    e = event_sample(frame, nfft, hop, place)
+    C = len(levels)
+    x = np.zeros((n, C), dtype=np.float32)
+    for c in range(C):
+        f1, f2 = rng.uniform(0.05, 0.45, size=2)
+        ph = rng.uniform(0, 2*np.pi, size=2)
+        s = np.sin(2*np.pi*f1*t + ph[0]) + 1e-4*np.sin(2*np.pi*f2*t + ph[1]) + 1e-6*rng.standard_normal(n)
+        if name == 'fall':
+            s[:e] += S
+        elif name == 'rise':
+            s[e:] += S
+        elif name == 'staircase':
+            every = 3 if nseg >= 7 else 1
+            at = [event_sample(j, nfft, hop, place) for j in range(every, nseg, every)]
+            sizes = [S*(1.0, 0.25, 0.75, 0.1, 0.5, 0.05)[k % 6] for k in range(len(at))]
+            sizes[-1] = 0.0
+            for k, a in enumerate(at):
+                s[a:at[k + 1] if k + 1 < len(at) else n] += sizes[k]
+        elif name == 'burst':
+            s[e:e + 3*hop] *= 1e6
+        elif name == 'silence':
+            nz = 3 if nseg >= 7 else 1
+            for a, b in ((frame*hop, (frame + nz - 1)*hop + nfft), ((nseg - 1)*hop, n)):
+                s[a:b] = floor*rng.standard_normal(max(min(b, n) - a, 0)) if floor else 0.0
+        elif name == 'pulses':
+            s[(0 if c % 2 == 0 else hop - 1)::hop] += 1e3
+        elif name == 'transient':
+            s[e:] += S*np.exp(-(t[e:] - e)/(2.0*hop))
+        else:
+            raise ValueError(name)
+        x[:, c] = (levels[c]*s).astype(np.float32)
+    return x
