@@ -68,6 +68,26 @@ def _subtract(ranges, a, b):
     return out
 
 
+def _regrid(trace, step, count):
+    """One frame of `trace` per `step` frames of its source from now on, the source holding `count` frames: rate, frames
+    and shape (update_step), then offset and bufferframes as align_buffer computes them -- without moving anything, the
+    recompute that follows allocates for them.  The traces below keep their own steps and follow."""
+    ratios = [max(1, int(round(trace.rate/d.rate))) for d in trace.dests]
+    trace.update_step(step, tuple(trace.shape[2:]) or None)
+    src = trace.source
+    first = src.offset
+    reaches_end = first + count >= src.frames
+    if first > 0:
+        margin = floor(trace.source_tbefore*src.rate)
+        first, count = first + margin, count - margin
+    if not reaches_end:
+        count -= floor(trace.source_tafter*src.rate)
+    trace.offset = trace._own_frames(first, up=True)
+    trace.bufferframes = max(0, min(trace._own_frames(first + count), trace.frames) - trace.offset)
+    for d, r in zip(trace.dests, ratios):
+        _regrid(d, r, trace.bufferframes)
+
+
 class _LazyBuffer(object):
     """What ``trace.buffer`` returns while parts of the host copy are stale: it looks like the
     (frames, channels[, F]) float64 array, but only copies back from the device mirror the
@@ -871,6 +891,30 @@ class BufferedData(BufferedArray):
         src = self.source
         return src._hostbuf if isinstance(src, BufferedData) else src.buffer
 
+    def _whole_step(self):
+        """Source frames per frame of this trace when that is a whole number (update_step's step), else None."""
+        ratio = self.source.rate/self.rate
+        step = int(round(ratio))
+        return step if step >= 1 and abs(ratio - step) <= 1e-9*step else None
+
+    def _source_frames(self, frames, up=False):
+        """The position `frames` of this trace in frames of its source, rounded down (`up`: up).  A whole step is exact
+        integer arithmetic: through a rate like 8000/3 the floating-point product is one frame off at some positions,
+        which shifted a strip by a source frame or made its slab one frame too long."""
+        step = self._whole_step()
+        if step is not None:
+            return int(frames)*step
+        x = frames*self.source.rate/self.rate
+        return ceil(x) if up else floor(x)
+
+    def _own_frames(self, frames, up=False):
+        """The position `frames` of the source in frames of this trace, rounded down (`up`: up)."""
+        step = self._whole_step()
+        if step is not None:
+            return -(-int(frames)//step) if up else int(frames)//step
+        x = frames*self.rate/self.source.rate
+        return ceil(x) if up else floor(x)
+
     def align_buffer(self):
         """Put this buffer over what the source holds minus the margins the computation needs:
         `source_tbefore` at the front unless the source starts at the beginning of the recording,
@@ -883,8 +927,8 @@ class BufferedData(BufferedArray):
             first, count = first + margin, count - margin
         if not reaches_end:
             count -= floor(self.source_tafter*src.rate)
-        offset = ceil(first*self.rate/src.rate)
-        self.move_buffer(offset, floor((first + count)*self.rate/src.rate) - offset)
+        offset = self._own_frames(first, up=True)
+        self.move_buffer(offset, self._own_frames(first + count) - offset)
         self.bufferframes = len(self._hostbuf)
 
     def _load_geometry(self, offset, nframes):
@@ -894,8 +938,8 @@ class BufferedData(BufferedArray):
         (buffereddata.py:93-107)."""
         src = self.source
         # the same span in source frames
-        first = floor(offset*src.rate/self.rate)
-        count = ceil((offset + nframes)*src.rate/self.rate) - first
+        first = self._source_frames(offset)
+        count = self._source_frames(offset + nframes, up=True) - first
         # Margins.  The reference DIVIDES the margins in seconds by the rate where it means to
         # multiply (buffereddata.py:96,99), which for any real rate gives no frame before and one
         # frame after.  Kept as it is: it decides what process() gets to see.

@@ -5,11 +5,9 @@ ship.  Written as a plain plug-in it would be ``np.convolve(source[:, c], kernel
 launch on the source's device mirror (float32 products on the matrix cores), and a new kernel recomputes this trace
 only.  ``kernel_bank()`` runs a whole bank (one feature trace per kernel) in one pass."""
 
-from math import ceil
-
 import numpy as np
 
-from .buffereddata import BufferedData, _KEEP
+from .buffereddata import BufferedData, _KEEP, _regrid
 
 MAX_KERNELS = 16
 
@@ -91,12 +89,8 @@ class BufferedKernelFilter(BufferedData):
             self.threshold = None if threshold is None else float(threshold)
         if step is not None and max(1, int(step)) != self.step:
             self.step = max(1, int(step))
-            self.update_step(self.step)
-            # the buffer over what the source holds, as align_buffer would put it (no margins)
-            src = self.source
-            first, count = src.offset, self._source_len()
-            self.offset = ceil(first/self.step)
-            self.bufferframes = max(0, min((first + count)//self.step, self.frames) - self.offset)
+            # the buffer over what the source holds, as align_buffer would put it; the traces below follow the new grid
+            _regrid(self, self.step, self._source_len())
         self._set_range()
         self.recompute_all()
 

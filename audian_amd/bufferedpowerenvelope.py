@@ -5,11 +5,9 @@ cut-off).  ``process()`` is one ``hipdsp_power_envelope`` call on the source's d
 nothing written at full rate.  This is NOT ``BufferedEnvelope`` (``pi/2 |x|`` filtered at second order, at full rate): it
 is the trace the detector's thresholds, events and pulse rates are defined on."""
 
-from math import ceil, floor
-
 import numpy as np
 
-from .buffereddata import BufferedData, _KEEP
+from .buffereddata import BufferedData, _KEEP, _regrid      # (_regrid lived here first: it stays importable)
 from .design import butter_sos
 
 
@@ -47,26 +45,6 @@ def power_envelope_host(sos, slab, first=0, step=1, n_out=None, gain=4.0, root=T
         f = _sosfilt(sos, y[::-1], zi*y[-1])[::-1][edge:edge + frames]
         out[:, c] = (float(gain)*np.maximum(f[first::step][:n_out], 0.0)).astype(np.float32)
     return np.sqrt(out) if root else out
-
-
-def _regrid(trace, step, count):
-    """One frame of `trace` per `step` frames of its source from now on, the source holding `count` frames: rate, frames
-    and shape (update_step), then offset and bufferframes as align_buffer computes them -- without moving anything, the
-    recompute that follows allocates for them.  The traces below keep their own steps and follow."""
-    ratios = [max(1, int(round(trace.rate/d.rate))) for d in trace.dests]
-    trace.update_step(step, tuple(trace.shape[2:]) or None)
-    src = trace.source
-    first = src.offset
-    reaches_end = first + count >= src.frames
-    if first > 0:
-        margin = floor(trace.source_tbefore*src.rate)
-        first, count = first + margin, count - margin
-    if not reaches_end:
-        count -= floor(trace.source_tafter*src.rate)
-    trace.offset = ceil(first*trace.rate/src.rate)
-    trace.bufferframes = max(0, min(floor((first + count)*trace.rate/src.rate), trace.frames) - trace.offset)
-    for d, r in zip(trace.dests, ratios):
-        _regrid(d, r, trace.bufferframes)
 
 
 class BufferedPowerEnvelope(BufferedData):

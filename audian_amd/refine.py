@@ -103,16 +103,17 @@ def _zi(sos):
 
 
 def _sosfilt(sos, x, z):
-    y = np.empty(len(x))
-    z = [list(v) for v in z]
-    for i, cur in enumerate(x):
-        for s, (b0, b1, b2, _, a1, a2) in enumerate(sos):
-            out = b0*cur + z[s][0]
-            z[s][0] = b1*cur - a1*out + z[s][1]
-            z[s][1] = b2*cur - a2*out
-            cur = out
-        y[i] = cur
-    return y
+    """The cascade in direct form II transposed from the state z (S, 2), section after section over the whole sequence, on
+    Python floats: the same IEEE double arithmetic as numpy scalars sample by sample, in a tenth of the time."""
+    y = np.asarray(x, dtype=np.float64).tolist()
+    for (b0, b1, b2, _, a1, a2), (z0, z1) in zip(np.asarray(sos, dtype=np.float64).tolist(),
+                                                 np.asarray(z, dtype=np.float64).tolist()):
+        for i, cur in enumerate(y):
+            out = b0*cur + z0
+            z0 = b1*cur - a1*out + z1
+            z1 = b2*cur - a2*out
+            y[i] = out
+    return np.array(y, dtype=np.float64)
 
 
 def check_sos(sos):

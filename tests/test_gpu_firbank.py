@@ -392,7 +392,7 @@ class Item:
 
 
 @pytest.mark.parametrize('step', [1, 48])
-def test_kernel_filter_trace_below_the_envelope(step):
+def test_kernel_filter_trace_below_the_envelope(oracle, step):
     from audian_amd import hipdsp
     from audian_amd.bufferedenvelope import BufferedEnvelope
     from audian_amd.bufferedfilter import BufferedFilter
@@ -400,7 +400,7 @@ def test_kernel_filter_trace_below_the_envelope(step):
     from audian_amd.design import gabor_kernels
     from audian_amd.tracegraph import TraceGraph
     rate, C = 48000.0, 3
-    n = int(20*rate)
+    n = int(30*rate)                     # (long enough for the loader's buffer to leave the start of the recording)
     rng = np.random.default_rng(step)
     tt = np.arange(n)/rate
     x = (0.5 + 0.4*np.sin(2*np.pi*7.0*tt))[:, None]*np.sin(2*np.pi*3000.0*tt)[:, None]*np.array([1.0, 0.5, 0.1]) + \
@@ -438,8 +438,16 @@ def test_kernel_filter_trace_below_the_envelope(step):
         assert np.max(np.abs(want)) > 0.01
 
     started = hipdsp.launches.get('fir_bank', 0)
+    from facade_ledger import Ledger
+    ledger = Ledger(g, oracle, only=('features',))
     for t0, t1 in [(0.0, 2.0), (1.0, 3.0), (9.0, 11.0), (17.5, 19.9)]:
         g.update_times(t0, t1)
+    # a scrolled state: the overlap recycled on the device, the new strip computed from a zero-extended slab at `step`
+    kept = (feat.offset, len(feat.buffer))
+    g.update_times(24.5, 26.5)
+    assert feat.offset > kept[0] and feat.offset < kept[0] + kept[1] and ledger.stats['features']['partial'] >= 1
+    ledger.check(flush=False)            # (read from the mirror: the host copy stays stale for what follows)
+    ledger.close()
     assert hipdsp.launches.get('fir_bank', 0) > started and feat._stale      # the device path, not the host fallback
     seen = dict(counts)
     before = dict(hipdsp.launches)
