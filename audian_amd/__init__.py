@@ -8,3 +8,15 @@ that computes) loads ``libhip_dsp.so`` and fails loudly if it is missing.
 """
 
 __version__ = '0.1.0'
+
+# names resolved on first use, so that importing the package stays free of side effects
+_EXPORTS = {'NoiseProfile': 'noiseprofile', 'host_bin_quantiles': 'noiseprofile', 'host_equalize': 'noiseprofile',
+            'BufferedEqualizedSpectrogram': 'bufferedequalizedspectrogram'}
+__all__ = sorted(_EXPORTS)
+
+
+def __getattr__(name):
+    if name in _EXPORTS:
+        from importlib import import_module
+        return getattr(import_module('.' + _EXPORTS[name], __name__), name)
+    raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

@@ -297,6 +297,58 @@ class BufferedSpectrogram(BufferedData):
             rows = host_spectral_features(self.buffer[a:b], k0, k1, mask, self.fresolution, min_power, drop_db)
         return {name: np.ascontiguousarray(rows[j]) for j, name in enumerate(names)}
 
+    @property
+    def sample_rate(self):
+        """The rate of the samples the windows are cut from (a spectrogram-shaped trace derived from this one passes its
+        source's on)."""
+        return self.source.rate
+
+    def _recording_samples(self):
+        """Samples of the recording this spectrogram's frames are windows of."""
+        return int(self.source.frames)
+
+    def complete_frames(self):
+        """Frames (absolute, from the start of the recording) whose window lies inside the recording; the ones behind
+        them are the zero tail."""
+        n = self._recording_samples()
+        return 0 if n < self.nfft else (n - self.nfft)//self.hop + 1
+
+    def noise_profile(self, i0, i1, percentile=50.0, frame_step=1, min_power=1e-20):
+        """The noise profile (noiseprofile.NoiseProfile) of frames [i0, i1) (absolute frame indices inside the current
+        buffer), every `frame_step`-th of them: per channel and bin the `percentile` over time, linearly interpolated
+        as np.percentile does.  Frames past the last complete window of the recording (the zero tail) are left out.
+        With a valid device mirror ONE hipdsp_bin_quantiles call selects the two order statistics of every column
+        (an exact radix select); 2*4 + 4 bytes per column come back and the host interpolates in float64.  Otherwise
+        numpy on the host buffer (noiseprofile.host_bin_quantiles): the same bits."""
+        from . import hipdsp
+        from .noiseprofile import NoiseProfile, finish_quantiles, host_bin_quantiles
+        F = self.nfft//2 + 1
+        a, b = int(i0) - self.offset, int(i1) - self.offset
+        n = len(self._hostbuf)
+        frame_step = int(frame_step)
+        if a < 0 or b > n or b < a:
+            raise IndexError('range outside the loaded buffer')
+        if frame_step < 1 or not 0.0 <= float(percentile) <= 100.0:
+            raise ValueError('frame_step must be at least 1 and percentile within 0 ... 100')
+        q = float(percentile)/100.0
+        b = max(a, min(b, self.complete_frames() - self.offset))
+        n_frames = (b - a + frame_step - 1)//frame_step
+        if n_frames > 0 and self.channels > 0 and self._mirror_valid(a, b):
+            out = hipdsp.DeviceArray(self.ctx, (self.channels, F, 2), np.float32)
+            cnt = hipdsp.DeviceArray(self.ctx, (self.channels, F), np.int32)
+            try:
+                hipdsp.bin_quantiles(self.ctx, self._dev, self._pitch(), self.channels, n, F, a, n_frames, frame_step, 0, F, q,
+                                     out, cnt)
+                lo_hi, count = out.to_host(), cnt.to_host()
+            finally:
+                out.free()
+                cnt.free()
+        else:
+            lo_hi, count = host_bin_quantiles(self.buffer[a:b] if b > a else np.zeros((0, self.channels, F)), 0, n_frames,
+                                              frame_step, 0, F, q)
+        return NoiseProfile(finish_quantiles(lo_hi, count, q).astype(np.float32), self.fresolution, self.tresolution,
+                            percentile, min_power, (a + self.offset)/self.rate, (b + self.offset)/self.rate)
+
     def estimate_noiselevels(self, channel):
         """Colour range for the spectrogram image (bufferedspectrogram.py:109-126): 95th
         percentile of the dB values in the top 1/16 of the band, and the maximum dB.  With a

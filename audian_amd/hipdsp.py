@@ -686,6 +686,37 @@ def spectral_features(ctx, spec, spec_pitch, channels, frames, nfreq, k0, k1, fe
                                        int(out_pitch), int(out_feature_pitch)))
 
 
+EQ_MODES = {'divide': 0, 'subtract': 1}          # HIPDSP_EQ_ in include/hip_dsp.h
+
+
+def eq_mode(mode):
+    """HIPDSP_EQ_DIVIDE / HIPDSP_EQ_SUBTRACT of 'divide' / 'subtract' (or of the number itself); ValueError else."""
+    if mode in EQ_MODES:
+        return EQ_MODES[mode]
+    if mode in (0, 1) and not isinstance(mode, bool):
+        return int(mode)
+    raise ValueError(f'unknown equalisation mode {mode!r}: one of {", ".join(EQ_MODES)}')
+
+
+def bin_quantiles(ctx, spec, spec_pitch, channels, frames, nfreq, first, n_frames, frame_step, k0, k1, q, out_lo_hi,
+                  out_count=None):
+    """out_lo_hi[c, k - k0] = the two order statistics v[floor(q (n-1))], v[min(that + 1, n-1)] of the n non-NaN values
+    spec[c, first + j*frame_step, k], j < n_frames, out_count[c, k - k0] = n (hipdsp_bin_quantiles): an exact radix
+    select per column of the slab."""
+    _count('bin_quantiles')
+    check(lib.hipdsp_bin_quantiles(ctx.handle, _p(spec), int(spec_pitch), int(channels), int(frames), int(nfreq),
+                                   int(first), int(n_frames), int(frame_step), int(k0), int(k1), float(q), _p(out_lo_hi),
+                                   _p(out_count)))
+
+
+def spec_equalize(ctx, spec, spec_pitch, out, out_pitch, channels, frames, nfreq, profile, profile_pitch=0, mode='divide'):
+    """out[c, t, k] = spec[c, t, k] / profile[c, k] ('divide') or max(spec[c, t, k] - profile[c, k], 0) ('subtract') in
+    numpy's float32 arithmetic (hipdsp_spec_equalize); out may be spec itself."""
+    _count('spec_equalize')
+    check(lib.hipdsp_spec_equalize(ctx.handle, _p(spec), int(spec_pitch), _p(out), int(out_pitch), int(channels),
+                                   int(frames), int(nfreq), _p(profile), int(profile_pitch), eq_mode(mode)))
+
+
 def fir_bank(ctx, plan, x, x_pitch, channels, frames, first, step, n_out, out, rectify=False, out_pitch=0,
              out_kernel_pitch=0):
     """out[k, c, i] = sum_j taps[k, j] * x[c, first + i*step + (L-1)//2 - j] for every kernel of `plan`, x zero outside

@@ -253,7 +253,7 @@ class TraceGraph(object):
         frame and channel, and the per-event reduction runs on the host."""
         from .contours import CONTOUR_FEATURES, Contours, frame_table
         spec = self[spec_name]
-        rate = spec.source.rate
+        rate = spec.sample_rate
         table = frame_table(rows, rate, spec.nfft, spec.hop, spec.frames)
         a = int(table[:, 1].min()) if len(table) else spec.offset
         b = max(a, int(table[:, 2].max())) if len(table) else a
@@ -355,6 +355,20 @@ class TraceGraph(object):
             best.append(np.array([m[3] for m in merged], dtype=np.int64))
             best_r.append(np.array([m[2] for m in merged], dtype=np.float64))
         return Events(pairs, spec.rate, spec.name), best, best_r
+
+    # ---- noise profile -----------------------------------------------------------------------------
+    def estimate_noise_profile(self, t0=None, t1=None, percentile=50.0, spec_name='spectrogram', frame_step=1,
+                               min_power=1e-20):
+        """The noise profile (noiseprofile.NoiseProfile) of the spectrogram `spec_name` between t0 and t1 seconds (by
+        default its current buffer): per channel and bin the `percentile` over every `frame_step`-th frame.  The buffers
+        are moved as in detect_events, then BufferedSpectrogram.noise_profile (on the device mirror when the trace has
+        one: one radix select per column, twelve bytes per column come back).  What BufferedEqualizedSpectrogram
+        .set_profile takes."""
+        spec = self[spec_name]
+        i0, i1 = self._event_frames(spec, t0, t1)
+        if i0 is None:
+            i0, i1 = spec.offset, spec.offset + len(spec._buf())
+        return spec.noise_profile(i0, i1, percentile, frame_step, min_power)
 
     def attribute_events(self, events, trace_name=None, max_delay=0.001, channels=None, min_r=0.5, min_ratio=1.0):
         """event_cross_correlation followed by the attribution rule (xcorr.attribute_events, whose two thresholds are

@@ -628,6 +628,54 @@ int hipdsp_spectral_features(hipdsp_ctx *ctx, const float *spec, int64_t spec_pi
                              double scale, double min_power, double drop_ratio, float *out, int64_t out_pitch,
                              int64_t out_feature_pitch);
 
+/* Per-bin order statistics over time: the noise profile of a spectrogram (a percentile of every frequency bin, which a
+ * stationary band -- mains hum, an insect chorus, microphone noise -- dominates and a call does not).  spec, spec_pitch
+ * and the alignment-free rows are those of hipdsp_band_power.  For channel c and bin k in [k0, k1) the input set is
+ *   spec[c, first + j*frame_step, k],  j < n_frames         (first >= 0, first + (n_frames-1)*frame_step < frames)
+ * with the NaNs dropped: n values remain, v[0..n-1] ascending by value (infinities included, -0 equal to +0).  With
+ *   pos = q*(double)(n - 1)   (one double multiply),   k_lo = floor(pos),   k_hi = min(k_lo + 1, n - 1)
+ * the call stores, at column i = c*(k1 - k0) + (k - k0),
+ *   out_lo_hi[2*i] = v[k_lo],  out_lo_hi[2*i + 1] = v[k_hi],  out_count[i] = n      (out_count may be NULL)
+ * and NaN, NaN, 0 for a column without a value (n == 0, also n_frames == 0).  Both values are elements of the input,
+ * bit for bit; the sign of a returned zero is unspecified.  The host finishes the percentile as np.percentile does:
+ * frac = pos - k_lo, the result is lo when frac == 0 or hi == lo, else lo + frac*(hi - lo) in float64.  The profile is
+ * the percentile itself: no bias correction of a median towards the mean of periodogram values is applied.
+ * HIPDSP_ERR_INVALID: NULL ctx, q outside [0, 1] or NaN, a band outside [0, nfreq], frame_step < 1, a frame range
+ * outside [0, frames), a negative size, a pitch too small, NULL spec or out_lo_hi with work to do, an output that
+ * overlaps the slab or the other output, frames*nfreq or spec_pitch beyond 2^44 elements.
+ * HIPDSP_ERR_UNSUPPORTED: n_frames >= 2^31 (the counters are 32-bit), more than 65535 channels.  channels == 0 or
+ * k1 == k0: nothing is written.  A refused call writes nothing.
+ * Promises: an exact radix select, four passes of 8-bit digits over an order-preserving 32-bit key, each a read of the
+ * columns' elements (the requested frames of the band are read four times); no atomics on global memory (LDS
+ * counters only) and no context scratch; all scalars travel by value, the call is one kernel node inside
+ * hipdsp_graph_begin/end; the same call gives the same bits twice; a column's result depends on its own values alone,
+ * not on the other channels, on k0 / k1, on the pitch or on the tile of bins it falls in; only the requested elements
+ * are read and nothing outside the output rows is written; index arithmetic on the slab is 64-bit, rows start at any
+ * 4-byte address. */
+int hipdsp_bin_quantiles(hipdsp_ctx *ctx, const float *spec, int64_t spec_pitch, int64_t channels, int64_t frames,
+                         int64_t nfreq, int64_t first, int64_t n_frames, int64_t frame_step, int64_t k0, int64_t k1,
+                         double q, float *out_lo_hi, int32_t *out_count);
+
+/* Equalise a spectrogram slab by a per-channel, per-bin profile (hipdsp_bin_quantiles, finished on the host):
+ *   HIPDSP_EQ_DIVIDE    out[c, t, k] = float32((double)spec[c, t, k] / (double)profile[c, k])  -- the correctly rounded
+ *                       float32 quotient (53 >= 2*24 + 2), the whitened image
+ *   HIPDSP_EQ_SUBTRACT  out[c, t, k] = float32(spec[c, t, k] - profile[c, k]), then 0 where that is < 0 -- spectral
+ *                       subtraction
+ * NaN stays NaN, infinities and denormals as IEEE 754 and numpy's float32 arithmetic have them: both modes are bit for
+ * bit numpy's.  spec and out are planar (channels, frames, nfreq) slabs with spec_pitch / out_pitch elements between
+ * channels (0 = frames*nfreq); profile is a DEVICE array (channels, nfreq) float32 with profile_pitch elements between
+ * channels (0 = nfreq).  In place (out == spec with equal pitch) is allowed, any other overlap of out with spec or with
+ * the profile is HIPDSP_ERR_INVALID, as are NULL pointers with work to do, negative sizes, a pitch too small, frames*nfreq
+ * or a pitch beyond 2^44 elements and an unknown mode; more than 65535 channels is HIPDSP_ERR_UNSUPPORTED.  A refused call writes nothing; channels, frames or
+ * nfreq == 0 writes nothing.  Promises: one streaming pass, one kernel node inside hipdsp_graph_begin/end, no atomics,
+ * no context scratch, the same bits twice, a value depends on its own element and its profile entry alone, 64-bit index
+ * arithmetic, rows at any 4-byte address (16-byte accesses only where both slabs allow them). */
+#define HIPDSP_EQ_DIVIDE 0
+#define HIPDSP_EQ_SUBTRACT 1
+int hipdsp_spec_equalize(hipdsp_ctx *ctx, const float *spec, int64_t spec_pitch, float *out, int64_t out_pitch,
+                         int64_t channels, int64_t frames, int64_t nfreq, const float *profile, int64_t profile_pitch,
+                         int mode);
+
 /* ---- FIR kernel bank ("feature expansion (kernel filter)") ----------------- */
 
 /* A plan holds, in device memory, the taps and thresholds of up to 16 FIR kernels of one common length, as

@@ -168,6 +168,27 @@ for b in builds:
     if b is builds[-1]:
         print(logs[b['name']][-1], flush=True)
     plan.close()
+# ---- hipdsp_bin_quantiles / hipdsp_spec_equalize over the same PSD slab: the per-bin median, and the slab divided by it
+# (tools/noise_profile_bench.py has the slab with ties, the other mode, in place, and the copy of the slab as a yardstick)
+for b in builds:
+    h, ctx = b['h'], b['ctx']
+    if not hasattr(h.lib, 'hipdsp_bin_quantiles'):
+        continue
+    ds, out = b['buf']['ds'], b['buf']['db']
+    lo_hi, count = h.DeviceArray(ctx, (C, F, 2), np.float32), h.DeviceArray(ctx, (C, F), np.int32)
+    ms = min(timed(b, lambda: h.bin_quantiles(ctx, ds, 0, C, nd, F, 0, nd, 1, 0, F, 0.5, lo_hi, count), 3) for _ in range(rounds))
+    ctx.synchronize()
+    logs[b['name']].append(f'{"hipdsp_bin_quantiles over the PSD 2048/1024, q 0.5 (four reads of the slab)":78s} {ms:8.3f} ms {16.0*C*nd*F/ms/1e6:7.0f} GB/s')
+    if b is builds[-1]:
+        print(logs[b['name']][-1], flush=True)
+    prof = h.DeviceArray.from_host(ctx, np.maximum(lo_hi.to_host()[:, :, 0], np.float32(1e-20)))
+    ms = min(timed(b, lambda: h.spec_equalize(ctx, ds, 0, out, 0, C, nd, F, prof, 0, 'divide'), 5) for _ in range(rounds))
+    ctx.synchronize()
+    logs[b['name']].append(f'{"hipdsp_spec_equalize over the PSD 2048/1024, divide, out of place":78s} {ms:8.3f} ms {8.0*C*nd*F/ms/1e6:7.0f} GB/s')
+    if b is builds[-1]:
+        print(logs[b['name']][-1], flush=True)
+    for d in (lo_hi, count, prof):
+        d.free()
 # ---- hipdsp_fir_bank: 16 kernels of 257 taps over the envelope, one frame per millisecond (tools/fir_bank_bench.py has the
 # other kernel lengths and steps)
 for b in builds:
