@@ -235,7 +235,7 @@ class BufferedData(BufferedArray):
     _ctx = None
     _fused_token = False       # the source's own launch has already filled this trace's whole buffer (mirror)
     _alias_pitch = None        # the mirror is a VIEW of another device array with this row pitch (_alias_mirror)
-    _plan = None               # the device plan of self.sos and the bytes it was set from (_sos_plan)
+    _plan = None               # the trace's device plan and the key of what it was set from last (_keyed_plan)
     _plan_key = None
 
     def __init__(self, name, source_name, tbefore=0, tafter=0, panel='none', panel_type='trace',
@@ -567,16 +567,21 @@ class BufferedData(BufferedArray):
         from . import hipdsp
         hipdsp.envelope(self.ctx, None, None, 0, ddst, dpitch, self.channels, n, 0)
 
-    def _sos_plan(self):
-        """The SosPlan of self.sos: created once, set again only when the table's bytes change."""
-        from . import hipdsp
-        key = self.sos.tobytes()
+    def _keyed_plan(self, kind, key, *args):
+        """This trace's device plan, a hipdsp `kind`: created once, set(*args) again only when `key` -- the bytes and
+        values `args` stand for -- differs from the key of the last set.  Keyed by content: an object's identity is reused
+        as soon as the object before is gone."""
         if self._plan is None:
-            self._plan = hipdsp.SosPlan(self.ctx, self.sos)
-        elif key != self._plan_key:
-            self._plan.set(self.sos)
-        self._plan_key = key
+            self._plan = kind(self.ctx)
+        if key != self._plan_key:
+            self._plan.set(*args)
+            self._plan_key = key
         return self._plan
+
+    def _sos_plan(self):
+        """The SosPlan of self.sos."""
+        from . import hipdsp
+        return self._keyed_plan(hipdsp.SosPlan, self.sos.tobytes(), self.sos)
 
     def minmax_decimate(self, start, stop, step, channel=None):
         """Min/max screen decimation of frames [start, stop) (absolute frame indices inside

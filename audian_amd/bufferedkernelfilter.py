@@ -52,8 +52,6 @@ class BufferedKernelFilter(BufferedData):
         self.step = max(1, int(step))
         self.threshold = None if threshold is None else float(threshold)
         self.kernel = self._taps(kernel)
-        self._plan = None
-        self._plan_key = None
 
     @staticmethod
     def _taps(kernel):
@@ -95,13 +93,8 @@ class BufferedKernelFilter(BufferedData):
         self.recompute_all()
 
     def _device_plan(self, hipdsp):
-        key = (self.kernel.tobytes(), self.threshold)
-        if self._plan is None:
-            self._plan = hipdsp.FirPlan(self.ctx)
-        if key != self._plan_key:
-            self._plan.set(self.kernel[None, :], None if self.threshold is None else [self.threshold])
-            self._plan_key = key
-        return self._plan
+        return self._keyed_plan(hipdsp.FirPlan, (self.kernel.tobytes(), self.threshold), self.kernel[None, :],
+                                None if self.threshold is None else [self.threshold])
 
     def process(self, source, dest, nbefore):
         """dest[i, c] = y[c, nbefore + i*step], y the kernel over the slab `source` zero-extended at both ends."""

@@ -39,8 +39,6 @@ class BufferedTemplateMatch(BufferedData):
         self.pivot = None if pivot is None else float(pivot)
         self.k0 = 0
         self.stale = False
-        self._plan = None
-        self._plan_key = None
 
     @staticmethod
     def _checked(template, normalize):
@@ -121,13 +119,8 @@ class BufferedTemplateMatch(BufferedData):
         BufferedData.recompute(self)
 
     def _device_plan(self, hipdsp):
-        key = (self.template.values.tobytes(), self.template.values.shape, self.normalize)
-        if self._plan is None:
-            self._plan = hipdsp.TmplPlan(self.ctx)
-        if key != self._plan_key:
-            self._plan.set(self.template.values, self.normalize)
-            self._plan_key = key
-        return self._plan
+        values = self.template.values
+        return self._keyed_plan(hipdsp.TmplPlan, (values.tobytes(), values.shape, self.normalize), values, self.normalize)
 
     def _span(self, s0, n):
         """(lo, hi): the frames of the source's buffer the windows of dest frames [s0, s0 + n) lie in -- beyond the slab

@@ -91,15 +91,21 @@ static inline int hd_launch_status(const char *what)
     return HIPDSP_OK;
 }
 
+// Do two byte ranges share memory?
+static inline bool hd_bytes_overlap(const void *a, long long a_bytes, const void *b, long long b_bytes)
+{
+    if (a == nullptr || b == nullptr || a_bytes <= 0 || b_bytes <= 0) return false;
+    const char *a0 = (const char *)a, *b0 = (const char *)b;
+    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
 // Do two planar float arrays (channels rows of `pitch` floats, `frames` used) share memory?  The sweeps are cut into
 // time segments that run concurrently and re-read their warm-up from the input: an output over the input is a race.
 static inline bool hd_planar_overlap(const float *a, long long a_pitch, long long a_frames, const float *b, long long b_pitch,
                                      long long b_frames, long long channels)
 {
-    if (a == nullptr || b == nullptr || channels <= 0 || a_frames <= 0 || b_frames <= 0) return false;
-    const char *a0 = (const char *)a, *a1 = (const char *)(a + (channels - 1) * a_pitch + a_frames);
-    const char *b0 = (const char *)b, *b1 = (const char *)(b + (channels - 1) * b_pitch + b_frames);
-    return a0 < b1 && b0 < a1;
+    if (channels <= 0 || a_frames <= 0 || b_frames <= 0) return false;
+    return hd_bytes_overlap(a, 4 * ((channels - 1) * a_pitch + a_frames), b, 4 * ((channels - 1) * b_pitch + b_frames));
 }
 #define HD_NO_OVERLAP(a, ap, af, b, bp, bf, channels, what)                                             \
     HD_REQUIRE(!hd_planar_overlap((a), (ap), (af), (b), (bp), (bf), (channels)), what " must not overlap")

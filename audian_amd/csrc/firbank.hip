@@ -24,11 +24,13 @@
 //              (34 floats apart: the 32 lanes a ds_read_b32 serves at once -- 16 outputs x 2 slots -- fall on the 32
 //              banks 2m + i), restaged for every 32 taps.
 // The taps go through LDS in pieces of TAPS_KB slots.  The epilogue (threshold, max) runs on the VALU; the accumulators
-// are transposed through LDS so that a kernel's row is stored along time.
+// are transposed through LDS so that a kernel's row is stored along time.  The slot walk, the transpose, the store
+// loop and the host's checks of the output block are mfma_bank.h's, shared with templatematch.hip; the plan's staged
+// block is plan_stage.h's.
 // Samples outside [0, frames) are zeros; every global read is bounds-checked against frames, every store against
 // n_out and n_kernels.  Index arithmetic on the traces is 64-bit.
-#include "common.h"
-#include <atomic>
+#include "mfma_bank.h"
+#include "plan_stage.h"
 #include <cstddef>
 
 namespace {
@@ -36,17 +38,16 @@ namespace {
 constexpr int MAX_KERNELS = 16;
 constexpr int MAX_TAPS = 4097;
 constexpr int MAX_TAPS4 = (MAX_TAPS + 3) / 4 * 4;
-constexpr int TAPS_KB = 128;                  // tap slots per B stage (8 KB)
 constexpr int WIN_K = 32, WIN_RS = 34;        // window layout: slots per row, floats between rows
 constexpr int DENSE_CAP = 17408;              // floats of trace a dense tile may stage (68 KB)
-constexpr int OUT_FLOATS = 4 * 16 * 72;       // the epilogue's transpose, MT = 4
 
 struct FirTaps {
     float threshold[MAX_KERNELS];
     float taps[MAX_TAPS4 * MAX_KERNELS];      // [slot i][kernel n] = float32(h_n[L-1-i]); zero beyond L and beyond n_kernels
 };
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+// bytes of a plan of L taps: what set_host writes and upload copies
+size_t fir_used(int L) { return offsetof(FirTaps, taps) + sizeof(float) * 16 * (size_t)((L + 3) & ~3); }
 
 enum { FIR_DENSE1 = 0, FIR_DENSE = 1, FIR_WINDOW = 2 };
 
@@ -108,70 +109,35 @@ __global__ __launch_bounds__(256) void fir_bank_kernel(const FirTaps *__restrict
             __syncthreads();
             // rows past `rows` read LDS nobody staged: their results are never stored, and a row of the MFMA only
             // depends on its own A row
-            auto k_step = [&](int k) {
+            mb_walk(nb, [&](int k) {
                 const float b = B[k * 16 + lane];
 #pragma unroll
                 for (int mt = 0; mt < MT; mt++) {
                     const float a = A[fir_slot<MODE>(mrow + 16 * mt, kb + k + kq, istep)];
                     acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc[mt], 0, 0, 0);
                 }
-            };
-            int k = 0;
-            for (; k + 16 <= nb; k += 16) {                // four steps' LDS reads in flight
-                k_step(k); k_step(k + 4); k_step(k + 8); k_step(k + 12);
-            }
-            for (; k < nb; k += 4) k_step(k);
+            });
         }
     }
-    // C layout: kernel n = lane & 15, time = 4*(lane >> 4) + r.  Transpose per wave: row n of O[wave] holds the wave's
-    // OT times from column n >> 2 on, rows ORS = 8 (mod 32) floats apart: the 32 lanes a ds_write_b32 serves at once
-    // (16 kernels x 2 values of lane >> 4) fall on the banks 8*(n & 3) + 4*(lane >> 4) + (n >> 2) (+ r + 16*mt) mod 32,
-    // each once; the reads walk a row
-    __syncthreads();
-    constexpr int OT = 16 * MT, ORS = MT == 4 ? 72 : 40;
-    float *O = A + wave * 16 * ORS;
-#pragma unroll
-    for (int mt = 0; mt < MT; mt++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) O[(lane & 15) * ORS + ((lane & 15) >> 2) + mt * 16 + 4 * kq + r] = acc[mt][r];
-    __syncthreads();
-    const long long i0 = tile0 + wave * OT;
-    float *oc = out + c * out_pitch;
-    for (int idx = lane; idx < nk * OT; idx += 64) {
-        const int n = idx / OT, tl = idx % OT;
-        if (i0 + tl < n_out) {
-            float v = O[n * ORS + (n >> 2) + tl];
-            if (rectify) {
-                const float d = v - plan->threshold[n];
-                v = (d > 0.0f || d != d) ? d : 0.0f;       // NaN stays NaN, as np.maximum
-            }
-            oc[n * out_kernel_pitch + i0 + tl] = v;
-        }
-    }
-}
-
-// More than 64 KB of dynamic LDS has to be asked for, per kernel: done for all five instantiations when a device's
-// first plan is created (and checked again at every call), so that no launch ever does it inside a capture.
-template <int MT, int MODE>
-hipError_t fir_raise_one()
-{
-    return hipFuncSetAttribute((const void *)fir_bank_kernel<MT, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (DENSE_CAP + DENSE_CAP / 32 + 64 + TAPS_KB * 16) * (int)sizeof(float));
+    __syncthreads();                                       // the trace has been read: the transpose takes its place
+    const float *O = mb_transpose<MT>(A, acc, wave, lane);
+    mb_store<MT>(O, lane, nk, tile0 + wave * 16 * MT, n_out, out + c * out_pitch, out_kernel_pitch,
+                 [&](float v, int n, int, long long) {
+                     if (!rectify) return v;
+                     const float d = v - plan->threshold[n];
+                     return (d > 0.0f || d != d) ? d : 0.0f;    // NaN stays NaN, as np.maximum
+                 });
 }
 
 std::atomic<int> fir_raised[64];
 
 int fir_raise_all(hipdsp_ctx *ctx)
 {
-    std::atomic<int> &done = fir_raised[ctx->device & 63];
-    if (done.load(std::memory_order_acquire)) return HIPDSP_OK;
-    HD_CHECK_HIP((fir_raise_one<4, FIR_DENSE1>()));
-    HD_CHECK_HIP((fir_raise_one<4, FIR_DENSE>()));
-    HD_CHECK_HIP((fir_raise_one<2, FIR_DENSE>()));
-    HD_CHECK_HIP((fir_raise_one<1, FIR_DENSE>()));
-    HD_CHECK_HIP((fir_raise_one<4, FIR_WINDOW>()));
-    done.store(1, std::memory_order_release);
-    return HIPDSP_OK;
+    return mb_raise_lds(ctx, fir_raised,
+                        {(const void *)fir_bank_kernel<4, FIR_DENSE1>, (const void *)fir_bank_kernel<4, FIR_DENSE>,
+                         (const void *)fir_bank_kernel<2, FIR_DENSE>, (const void *)fir_bank_kernel<1, FIR_DENSE>,
+                         (const void *)fir_bank_kernel<4, FIR_WINDOW>},
+                        (DENSE_CAP + DENSE_CAP / 32 + 64 + TAPS_KB * 16) * (int)sizeof(float));
 }
 
 template <int MT, int MODE>
@@ -190,12 +156,9 @@ int fir_launch(hipdsp_ctx *ctx, const FirTaps *dev, const float *x, long long x_
 }  // namespace
 
 struct hipdsp_firplan {
-    FirTaps *host;         // pinned
-    FirTaps *dev;
+    hd_plan_stage stage;   // a FirTaps
     int n_kernels, n_taps; // of the last set_host
     int up_kernels, up_taps; // of the last upload (0 before the first): what the device block holds
-    hipEvent_t uploaded;
-    bool valid;
 };
 
 extern "C" {
@@ -206,28 +169,11 @@ int hipdsp_firplan_create(hipdsp_ctx *ctx, hipdsp_firplan **out)
     *out = nullptr;
     HD_CHECK_HIP(hipSetDevice(ctx->device));
     hipdsp_firplan *p = new hipdsp_firplan();
-    p->host = nullptr; p->dev = nullptr; p->uploaded = nullptr; p->valid = false;
-    p->n_kernels = p->n_taps = p->up_kernels = p->up_taps = 0;
-    hipError_t e = hipHostMalloc((void **)&p->host, sizeof(FirTaps), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->dev, sizeof(FirTaps));
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&p->uploaded, hipEventDisableTiming);
-    if (e != hipSuccess) {
-        if (p->host) (void)hipHostFree(p->host);
-        if (p->dev) (void)hipFree(p->dev);
+    int rc = hd_stage_create(ctx, &p->stage, sizeof(FirTaps), true);   // uploads copy the used prefix only
+    if (rc == HIPDSP_OK) rc = fir_raise_all(ctx);
+    if (rc != HIPDSP_OK) {
+        hd_stage_destroy(ctx, &p->stage);
         delete p;
-        HD_CHECK_HIP(e);
-    }
-    memset(p->host, 0, sizeof(FirTaps));
-    // on the context's stream, waited for: ordered before every later upload and launch, whatever kind of stream it is
-    e = hipMemsetAsync(p->dev, 0, sizeof(FirTaps), ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    int rc = e == hipSuccess ? fir_raise_all(ctx) : HIPDSP_OK;
-    if (e != hipSuccess || rc != HIPDSP_OK) {
-        (void)hipEventDestroy(p->uploaded);
-        (void)hipHostFree(p->host);
-        (void)hipFree(p->dev);
-        delete p;
-        HD_CHECK_HIP(e);
         return rc;
     }
     *out = p;
@@ -238,10 +184,7 @@ int hipdsp_firplan_destroy(hipdsp_ctx *ctx, hipdsp_firplan *plan)
 {
     HD_REQUIRE(ctx != nullptr, "ctx is NULL");
     if (!plan) return HIPDSP_OK;
-    (void)hipStreamSynchronize(ctx->stream);
-    if (plan->uploaded) (void)hipEventDestroy(plan->uploaded);
-    if (plan->host) (void)hipHostFree(plan->host);
-    if (plan->dev) (void)hipFree(plan->dev);
+    hd_stage_destroy(ctx, &plan->stage);
     delete plan;
     return HIPDSP_OK;
 }
@@ -255,12 +198,10 @@ int hipdsp_firplan_set_host(hipdsp_ctx *ctx, hipdsp_firplan *plan, const double 
         hipdsp_set_error("at most %d kernels of %d taps per plan, got %d of %d", MAX_KERNELS, MAX_TAPS, n_kernels, n_taps);
         return HIPDSP_ERR_UNSUPPORTED;
     }
-    // the previous upload must have left the pinned staging block
-    if (plan->valid) HD_CHECK_HIP(hipEventSynchronize(plan->uploaded));
-    FirTaps *h = plan->host;
-    const int L4 = (n_taps + 3) & ~3;
-    const int old4 = (plan->n_taps + 3) & ~3;
-    memset(h, 0, offsetof(FirTaps, taps) + sizeof(float) * 16 * (size_t)(L4 > old4 ? L4 : old4));
+    const int rc = hd_stage_host_free(&plan->stage);
+    if (rc != HIPDSP_OK) return rc;
+    FirTaps *h = (FirTaps *)plan->stage.host;
+    memset(h, 0, fir_used(n_taps > plan->n_taps ? n_taps : plan->n_taps));
     for (int n = 0; n < n_kernels; n++) {
         h->threshold[n] = host_threshold ? (float)host_threshold[n] : 0.0f;
         for (int i = 0; i < n_taps; i++) h->taps[i * 16 + n] = (float)host_taps[(size_t)n * n_taps + (n_taps - 1 - i)];
@@ -274,15 +215,10 @@ int hipdsp_firplan_upload(hipdsp_ctx *ctx, hipdsp_firplan *plan)
 {
     HD_REQUIRE(ctx != nullptr && plan != nullptr, "NULL argument");
     HD_REQUIRE(plan->n_kernels > 0, "plan has no taps yet");
-    const int L4 = (plan->n_taps + 3) & ~3;
-    HD_CHECK_HIP(hipMemcpyAsync(plan->dev, plan->host, offsetof(FirTaps, taps) + sizeof(float) * 16 * (size_t)L4,
-                                hipMemcpyHostToDevice, ctx->stream));
+    const int rc = hd_stage_upload(ctx, &plan->stage, fir_used(plan->n_taps));
+    if (rc != HIPDSP_OK) return rc;
     plan->up_kernels = plan->n_kernels;
     plan->up_taps = plan->n_taps;
-    if (!hd_capturing(ctx)) {
-        HD_CHECK_HIP(hipEventRecord(plan->uploaded, ctx->stream));
-        plan->valid = true;
-    }
     return HIPDSP_OK;
 }
 
@@ -309,28 +245,18 @@ int hipdsp_fir_bank(hipdsp_ctx *ctx, const hipdsp_firplan *plan, const float *x,
     HD_REQUIRE(step >= 1, "step %lld must be at least 1", (long long)step);
     const int L = plan->n_taps, nk = plan->n_kernels;
     if (x_pitch == 0) x_pitch = frames;
-    if (out_pitch == 0) out_pitch = n_out;
-    if (out_kernel_pitch == 0) out_kernel_pitch = channels * out_pitch;
     HD_REQUIRE(x_pitch >= frames, "x_pitch smaller than frames");
-    HD_REQUIRE(out_pitch >= n_out, "out_pitch smaller than n_out");
-    if (n_out == 0 || channels == 0) return HIPDSP_OK;
-    HD_REQUIRE(out_kernel_pitch >= (channels - 1) * out_pitch + n_out, "out_kernel_pitch smaller than one kernel's block");
-    HD_REQUIRE(out != nullptr && (x != nullptr || frames == 0), "NULL data pointer");
-    HD_REQUIRE(channels <= 65535 && n_out <= (1LL << 36), "too many channels or outputs for one call");
+    bool empty;
+    int rc = mb_check_out("kernel", x, frames, channels, n_out, out, &out_pitch, &out_kernel_pitch, &empty);
+    if (rc != HIPDSP_OK || empty) return rc;
     HD_REQUIRE(first <= (1LL << 60) && n_out <= ((1LL << 60) - first) / step, "first + n_out*step out of range");
-    if (frames > 0) {
-        const char *x0 = (const char *)x, *x1 = (const char *)(x + (channels - 1) * x_pitch + frames);
-        const char *o0 = (const char *)out;
-        const char *o1 = (const char *)(out + (nk - 1) * out_kernel_pitch + (channels - 1) * out_pitch + n_out);
-        HD_REQUIRE(!(x0 < o1 && o0 < x1), "x and out must not overlap");
-    }
+    HD_REQUIRE(frames == 0 || !mb_out_overlaps(x, (channels - 1) * x_pitch + frames, out, nk, out_kernel_pitch, channels,
+                                               out_pitch, n_out), "x and out must not overlap");
     HD_CHECK_HIP(hipSetDevice(ctx->device));
-    {
-        const int rc = fir_raise_all(ctx);
-        if (rc != HIPDSP_OK) return rc;
-    }
+    rc = fir_raise_all(ctx);
+    if (rc != HIPDSP_OK) return rc;
     const int L4 = (L + 3) & ~3;
-    const FirTaps *dev = plan->dev;
+    const FirTaps *dev = (const FirTaps *)plan->stage.dev;
 #define FIR_GO(MT, MODE, AF)                                                                                            \
     return fir_launch<MT, MODE>(ctx, dev, x, x_pitch, channels, frames, first, step, n_out, L, nk, rectify ? 1 : 0, out, \
                                 out_pitch, out_kernel_pitch, (AF))

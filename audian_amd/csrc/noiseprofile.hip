@@ -256,13 +256,6 @@ int eq_launch(hipdsp_ctx *ctx, const float *spec, long long spec_pitch, float *o
     return hd_launch_status("spec_equalize_kernel");
 }
 
-bool bytes_overlap(const void *a, long long a_bytes, const void *b, long long b_bytes)
-{
-    if (a == nullptr || b == nullptr || a_bytes <= 0 || b_bytes <= 0) return false;
-    const char *a0 = (const char *)a, *b0 = (const char *)b;
-    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
 }  // namespace
 
 extern "C" int hipdsp_bin_quantiles(hipdsp_ctx *ctx, const float *spec, int64_t spec_pitch, int64_t channels, int64_t frames,
@@ -293,8 +286,8 @@ extern "C" int hipdsp_bin_quantiles(hipdsp_ctx *ctx, const float *spec, int64_t 
     HD_REQUIRE(out_lo_hi != nullptr && (spec != nullptr || n_frames == 0), "NULL data pointer");
     const long long cols = channels * (k1 - k0);
     const long long spec_bytes = 4 * ((channels - 1) * spec_pitch + frames * nfreq);
-    HD_REQUIRE(!bytes_overlap(out_lo_hi, 8 * cols, spec, spec_bytes) && !bytes_overlap(out_count, 4 * cols, spec, spec_bytes) &&
-               !bytes_overlap(out_lo_hi, 8 * cols, out_count, 4 * cols), "the outputs must not overlap the slab or each other");
+    HD_REQUIRE(!hd_bytes_overlap(out_lo_hi, 8 * cols, spec, spec_bytes) && !hd_bytes_overlap(out_count, 4 * cols, spec, spec_bytes) &&
+               !hd_bytes_overlap(out_lo_hi, 8 * cols, out_count, 4 * cols), "the outputs must not overlap the slab or each other");
     HD_CHECK_HIP(hipSetDevice(ctx->device));
     const dim3 grid((unsigned)((k1 - k0 + QT_COLS - 1) / QT_COLS), (unsigned)channels);
     hipLaunchKernelGGL(bin_quantiles_kernel, grid, dim3(QT_THREADS), 0, ctx->stream, spec, (long long)spec_pitch,

@@ -379,7 +379,7 @@ extern "C" int hipdsp_power_envelope(hipdsp_ctx *ctx, const hipdsp_sosplan *plan
                                      double gain, int root, float *y, int64_t y_pitch)
 {
     HD_REQUIRE(ctx != nullptr, "ctx is NULL");
-    HD_REQUIRE(plan != nullptr && plan->valid, "hipdsp_power_envelope: no plan, or a plan that has not been set");
+    HD_REQUIRE(plan != nullptr && plan->stage.valid, "hipdsp_power_envelope: no plan, or a plan that has not been set");
     HD_REQUIRE(channels >= 0 && frames >= 0 && n_out >= 0, "negative size");
     HD_REQUIRE(step >= 1, "step %lld < 1", (long long)step);
     HD_REQUIRE(first >= 0, "first %lld < 0", (long long)first);

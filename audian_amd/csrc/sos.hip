@@ -1013,17 +1013,13 @@ int hipdsp_sosplan_create(hipdsp_ctx *ctx, hipdsp_sosplan **out)
     *out = nullptr;
     HD_CHECK_HIP(hipSetDevice(ctx->device));
     hipdsp_sosplan *p = new hipdsp_sosplan();
-    p->host = nullptr; p->dev = nullptr; p->uploaded = nullptr; p->valid = false;
-    hipError_t e = hipHostMalloc((void **)&p->host, sizeof(SosPlanDev), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->dev, sizeof(SosPlanDev));
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&p->uploaded, hipEventDisableTiming);
-    if (e != hipSuccess) {
-        if (p->host) (void)hipHostFree(p->host);
-        if (p->dev) (void)hipFree(p->dev);
+    const int rc = hd_stage_create(ctx, &p->stage, sizeof(SosPlanDev), false);   // every upload copies the whole block
+    if (rc != HIPDSP_OK) {
         delete p;
-        HD_CHECK_HIP(e);
+        return rc;
     }
-    memset(p->host, 0, sizeof(SosPlanDev));
+    p->host = (SosPlanDev *)p->stage.host;
+    p->dev = (SosPlanDev *)p->stage.dev;
     *out = p;
     return HIPDSP_OK;
 }
@@ -1032,10 +1028,7 @@ int hipdsp_sosplan_destroy(hipdsp_ctx *ctx, hipdsp_sosplan *plan)
 {
     HD_REQUIRE(ctx != nullptr, "ctx is NULL");
     if (!plan) return HIPDSP_OK;
-    (void)hipStreamSynchronize(ctx->stream);
-    if (plan->uploaded) (void)hipEventDestroy(plan->uploaded);
-    if (plan->host) (void)hipHostFree(plan->host);
-    if (plan->dev) (void)hipFree(plan->dev);
+    hd_stage_destroy(ctx, &plan->stage);
     delete plan;
     return HIPDSP_OK;
 }
@@ -1049,10 +1042,10 @@ int hipdsp_sosplan_set_host(hipdsp_ctx *ctx, hipdsp_sosplan *plan, const double 
                          n_sections, MAXS);
         return HIPDSP_ERR_UNSUPPORTED;
     }
-    // the previous upload must have left the pinned staging block
-    if (plan->valid) HD_CHECK_HIP(hipEventSynchronize(plan->uploaded));
+    int rc = hd_stage_host_free(&plan->stage);
+    if (rc != HIPDSP_OK) return rc;
     SosPlanDev tmp;
-    int rc = hd_fill_plan(&tmp, host_sos, n_sections);
+    rc = hd_fill_plan(&tmp, host_sos, n_sections);
     if (rc != HIPDSP_OK) return rc;
     memcpy(plan->host, &tmp, sizeof(tmp));
     return HIPDSP_OK;
@@ -1062,13 +1055,7 @@ int hipdsp_sosplan_upload(hipdsp_ctx *ctx, hipdsp_sosplan *plan)
 {
     HD_REQUIRE(ctx != nullptr && plan != nullptr, "NULL argument");
     HD_REQUIRE(plan->host->n_sections > 0, "plan has no coefficients yet");
-    HD_CHECK_HIP(hipMemcpyAsync(plan->dev, plan->host, sizeof(SosPlanDev), hipMemcpyHostToDevice,
-                                ctx->stream));
-    if (!hd_capturing(ctx)) {
-        HD_CHECK_HIP(hipEventRecord(plan->uploaded, ctx->stream));
-        plan->valid = true;
-    }
-    return HIPDSP_OK;
+    return hd_stage_upload(ctx, &plan->stage, sizeof(SosPlanDev));
 }
 
 int hipdsp_sosplan_set(hipdsp_ctx *ctx, hipdsp_sosplan *plan, const double *host_sos, int n_sections)

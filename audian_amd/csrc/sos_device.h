@@ -2,13 +2,12 @@
 // the fused sweeps (chain.hip).  Everything sits in an anonymous namespace: each translation unit gets its own copy.
 #pragma once
 #include "common.h"
+#include "plan_stage.h"
 #include "sos_plan.h"
 
 struct hipdsp_sosplan {
-    SosPlanDev *host;      // pinned
-    SosPlanDev *dev;
-    hipEvent_t uploaded;
-    bool valid;
+    hd_plan_stage stage;
+    SosPlanDev *host, *dev;   // the stage's blocks, as the sweeps read them
 };
 
 // Non-finite samples (NaN, Inf).  In the reference a band-pass that has seen one stays NaN to the end of the slab

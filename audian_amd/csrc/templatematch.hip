@@ -2,9 +2,12 @@
 // along a band of bins of a planar spectrogram slab, raw (a 2-D correlation) or normalised (the Pearson coefficient of
 // template and patch), one score row per template and channel (include/hip_dsp.h).
 //
-// As hipdsp_fir_bank (firbank.hip, whose header is the longer story) this is a GEMM whose A matrix is never built:
-// with n = Tt*Fb the patch matrix has one row of n values per window, and window t's row is the slab's frames
-// t .. t+Tt-1.  The products run on v_mfma_f32_16x16x4_f32 (exact f32, a k-ordered fmaf chain):
+// A GEMM whose A matrix is never built: with n = Tt*Fb the patch matrix has one row of n values per window, and window
+// t's row is the slab's frames t .. t+Tt-1.  The fragment layout, the walk over a frame's bins, the transpose of the
+// accumulators and the store loop behind it, the raising of the LDS limit and the host's checks of the output block are
+// mfma_bank.h's, shared with hipdsp_fir_bank (firbank.hip); the plan's staged block is plan_stage.h's.  What is here
+// is the tile of the slab, the order of the slots, the band sums and the three epilogues.
+// The products run on v_mfma_f32_16x16x4_f32 (exact f32, a k-ordered fmaf chain):
 //     M = 16 window starts     lane l holds A[m = l & 15][k = l >> 4]: ONE LDS read at (frame m + a, bin b + (l >> 4))
 //                              of the staged tile;
 //     N = 16 templates         lane l holds B[k = l >> 4][n = l & 15]: the plan keeps the taps as (slot, template) rows
@@ -12,8 +15,8 @@
 //                              consecutive floats;
 //     K = 4 bins of one frame per step.
 // A workgroup of four waves owns TM = 64*MT = 256 consecutive windows of one channel; every wave carries MT = 4
-// independent accumulators that share each B fragment (firbank.hip: 40 cycles of dependent latency against 32 of
-// issue).  All 16 template columns are always computed, unused ones hold zero taps.
+// independent accumulators that share each B fragment (40 cycles of dependent latency against 32 of issue).  All 16
+// template columns are always computed, unused ones hold zero taps.
 //
 // The band is cut into chunks of FC bins (the last one shorter, rounded up to a multiple of 4 with zero taps AND zero
 // values).  Per chunk the (TM + Tt - 1) frames under the tile are staged once in LDS, rows RS = FC + 2 floats apart:
@@ -36,11 +39,12 @@
 // Tt ~ 100 (32 x 128: 39 + 8 + 10 KB), one for the longest templates.
 // Frames outside [0, frames) are staged as zeros (their windows store NaN); every global read is bounds-checked against
 // frames and the band, every store against n_out and the template count.  Index arithmetic on the slab is 64-bit.
-#include "common.h"
+#include "mfma_bank.h"
+#include "plan_stage.h"
 #include "decibel.h"
-#include <atomic>
 #include <cmath>
 #include <cstddef>
+#include <vector>
 
 namespace {
 
@@ -48,9 +52,7 @@ constexpr int MAX_TEMPLATES = 16;
 constexpr int MAX_ROWS = 256;                 // Tt
 constexpr int MAX_TAPS = 65536;               // Tt * Fb
 constexpr int MAX_SLOTS = MAX_TAPS + 3 * MAX_ROWS;   // every frame of the last chunk padded to a multiple of 4
-constexpr int TAPS_KB = 128;                  // tap slots per B stage (8 KB)
 constexpr int TILE_CAP = 16384;               // floats of slab a tile may stage (64 KB)
-constexpr int OUT_FLOATS = 4 * 16 * 72;       // the epilogue's transpose
 constexpr int TM_MT = 4;                      // accumulators per wave: 64 windows each, 256 per workgroup
 
 struct TmplHead {
@@ -84,7 +86,8 @@ TmShape tm_shape(int Tt, int Fb)
     return s;
 }
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+// bytes of a plan of n_slots slots: what set_host writes and upload copies
+size_t tm_used(int n_slots) { return offsetof(TmplTaps, taps) + sizeof(float) * 16 * (size_t)n_slots; }
 
 struct TmArgs {
     long long spec_pitch, frames, first, n_out, out_pitch, out_template_pitch;
@@ -174,17 +177,12 @@ __global__ __launch_bounds__(256) void template_match_kernel(const TmplTaps *__r
             for (int a = 0; a < na; a++) {
                 const float *Ar = A + (mrow + a0 + a) * RS + kq;
                 const float *Br = B + a * w4 * 16 + lane;
-                auto k_step = [&](int b) {
+                mb_walk(w4, [&](int b) {
                     const float bv = Br[b * 16];
 #pragma unroll
                     for (int mt = 0; mt < MT; mt++)
                         acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(Ar[16 * mt * RS + b], bv, acc[mt], 0, 0, 0);
-                };
-                int b = 0;
-                for (; b + 16 <= w4; b += 16) {            // four steps' LDS reads in flight
-                    k_step(b); k_step(b + 4); k_step(b + 8); k_step(b + 12);
-                }
-                for (; b < w4; b += 4) k_step(b);
+                });
             }
         }
     }
@@ -202,35 +200,19 @@ __global__ __launch_bounds__(256) void template_match_kernel(const TmplTaps *__r
         OM[tid] = s1 / n;
         OD[tid] = (bad || !(D > g.thr)) ? (double)NAN : sqrt(D);
     }
-    // C layout: template n = lane & 15, window = 4*(lane >> 4) + r.  The transpose of firbank.hip: row n of O[wave]
-    // holds the wave's OT windows from column n >> 2 on, rows ORS = 8 (mod 32) floats apart
-    constexpr int OT = 16 * MT, ORS = 72;
-    float *O = A + wave * 16 * ORS;
-#pragma unroll
-    for (int mt = 0; mt < MT; mt++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) O[(lane & 15) * ORS + ((lane & 15) >> 2) + mt * 16 + 4 * kq + r] = acc[mt][r];
-    __syncthreads();
-    const long long i0 = tile0 + wave * OT;
-    float *oc = out + c * g.out_pitch;
-    for (int idx = lane; idx < g.nk * OT; idx += 64) {
-        const int n = idx / OT, tl = idx % OT;
-        const long long i = i0 + tl;
-        if (i >= g.n_out) continue;
-        const float G = O[n * ORS + (n >> 2) + tl];
-        const long long t = g.first + i;
-        float v;
-        if (t < 0 || t + Tt > g.frames) {
-            v = NAN;
-        } else if (NORM) {
-            const int o = wave * OT + tl;
-            v = (float)(((double)G - OM[o] * plan->head.h0[n]) / (plan->head.sq[n] * OD[o]));
-            v = v > 1.0f ? 1.0f : (v < -1.0f ? -1.0f : v);      // a coefficient; NaN stays
-        } else {
-            v = g.pivot == 0.0f ? G : (float)((double)G + (double)g.pivot * plan->head.h0[n]);
-        }
-        oc[n * g.out_template_pitch + i] = v;
-    }
+    constexpr int OT = 16 * MT;
+    const float *O = mb_transpose<MT>(A, acc, wave, lane);
+    mb_store<MT>(O, lane, g.nk, tile0 + wave * OT, g.n_out, out + c * g.out_pitch, g.out_template_pitch,
+                 [&](float G, int n, int tl, long long i) -> float {
+                     const long long t = g.first + i;
+                     if (t < 0 || t + Tt > g.frames) return NAN;
+                     if (NORM) {
+                         const int o = wave * OT + tl;
+                         const float v = (float)(((double)G - OM[o] * plan->head.h0[n]) / (plan->head.sq[n] * OD[o]));
+                         return v > 1.0f ? 1.0f : (v < -1.0f ? -1.0f : v);      // a coefficient; NaN stays
+                     }
+                     return g.pivot == 0.0f ? G : (float)((double)G + (double)g.pivot * plan->head.h0[n]);
+                 });
 }
 
 size_t tm_lds_bytes(int rows_lds, int a_floats)
@@ -240,25 +222,12 @@ size_t tm_lds_bytes(int rows_lds, int a_floats)
            (size_t)(a_floats + TAPS_KB * 16) * sizeof(float);
 }
 
-// More than 64 KB of dynamic LDS has to be asked for, per kernel: done for all instantiations when a device's first
-// plan is created (and checked again at every call), so that no launch ever does it inside a capture.
-template <bool NORM>
-hipError_t tm_raise_one()
-{
-    return hipFuncSetAttribute((const void *)template_match_kernel<NORM>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)tm_lds_bytes(256 + MAX_ROWS - 1, TILE_CAP));
-}
-
 std::atomic<int> tm_raised[64];
 
 int tm_raise_all(hipdsp_ctx *ctx)
 {
-    std::atomic<int> &done = tm_raised[ctx->device & 63];
-    if (done.load(std::memory_order_acquire)) return HIPDSP_OK;
-    HD_CHECK_HIP(tm_raise_one<true>());
-    HD_CHECK_HIP(tm_raise_one<false>());
-    done.store(1, std::memory_order_release);
-    return HIPDSP_OK;
+    return mb_raise_lds(ctx, tm_raised, {(const void *)template_match_kernel<true>, (const void *)template_match_kernel<false>},
+                        (int)tm_lds_bytes(256 + MAX_ROWS - 1, TILE_CAP));
 }
 
 template <bool NORM>
@@ -274,12 +243,9 @@ int tm_launch(hipdsp_ctx *ctx, const TmplTaps *dev, const float *spec, float *ou
 }  // namespace
 
 struct hipdsp_tmplplan {
-    TmplTaps *host;        // pinned
-    TmplTaps *dev;
+    hd_plan_stage stage;   // a TmplTaps
     int n_templates, rows, cols, normalize;          // of the last set_host
     int up_templates, up_rows, up_cols, up_normalize; // of the last upload (0 before the first): what the device block holds
-    hipEvent_t uploaded;
-    bool valid;
 };
 
 extern "C" {
@@ -342,29 +308,11 @@ int hipdsp_tmplplan_create(hipdsp_ctx *ctx, hipdsp_tmplplan **out)
     *out = nullptr;
     HD_CHECK_HIP(hipSetDevice(ctx->device));
     hipdsp_tmplplan *p = new hipdsp_tmplplan();
-    p->host = nullptr; p->dev = nullptr; p->uploaded = nullptr; p->valid = false;
-    p->n_templates = p->rows = p->cols = p->normalize = 0;
-    p->up_templates = p->up_rows = p->up_cols = p->up_normalize = 0;
-    hipError_t e = hipHostMalloc((void **)&p->host, sizeof(TmplTaps), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->dev, sizeof(TmplTaps));
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&p->uploaded, hipEventDisableTiming);
-    if (e != hipSuccess) {
-        if (p->host) (void)hipHostFree(p->host);
-        if (p->dev) (void)hipFree(p->dev);
+    int rc = hd_stage_create(ctx, &p->stage, sizeof(TmplTaps), true);   // uploads copy the used prefix only
+    if (rc == HIPDSP_OK) rc = tm_raise_all(ctx);
+    if (rc != HIPDSP_OK) {
+        hd_stage_destroy(ctx, &p->stage);
         delete p;
-        HD_CHECK_HIP(e);
-    }
-    memset(p->host, 0, sizeof(TmplTaps));
-    // on the context's stream, waited for: ordered before every later upload and launch, whatever kind of stream it is
-    e = hipMemsetAsync(p->dev, 0, sizeof(TmplTaps), ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    int rc = e == hipSuccess ? tm_raise_all(ctx) : HIPDSP_OK;
-    if (e != hipSuccess || rc != HIPDSP_OK) {
-        (void)hipEventDestroy(p->uploaded);
-        (void)hipHostFree(p->host);
-        (void)hipFree(p->dev);
-        delete p;
-        HD_CHECK_HIP(e);
         return rc;
     }
     *out = p;
@@ -375,10 +323,7 @@ int hipdsp_tmplplan_destroy(hipdsp_ctx *ctx, hipdsp_tmplplan *plan)
 {
     HD_REQUIRE(ctx != nullptr, "ctx is NULL");
     if (!plan) return HIPDSP_OK;
-    (void)hipStreamSynchronize(ctx->stream);
-    if (plan->uploaded) (void)hipEventDestroy(plan->uploaded);
-    if (plan->host) (void)hipHostFree(plan->host);
-    if (plan->dev) (void)hipFree(plan->dev);
+    hd_stage_destroy(ctx, &plan->stage);
     delete plan;
     return HIPDSP_OK;
 }
@@ -394,23 +339,17 @@ int hipdsp_tmplplan_set_host(hipdsp_ctx *ctx, hipdsp_tmplplan *plan, const doubl
                          MAX_ROWS, MAX_TAPS, n_templates, rows, cols);
         return HIPDSP_ERR_UNSUPPORTED;
     }
+    // validated and prepared before the block is waited for or touched: a refused set leaves the plan as it was
     const size_t m = (size_t)rows * cols;
-    float *taps = new float[m * n_templates];
+    std::vector<float> taps(m * n_templates);
     double h0[MAX_TEMPLATES], q[MAX_TEMPLATES];
-    int rc = hipdsp_template_prepare_host(host_templates, n_templates, rows, cols, normalize, taps, h0, q);
-    if (rc == HIPDSP_OK && plan->valid && hipEventSynchronize(plan->uploaded) != hipSuccess) {
-        // the previous upload must have left the pinned staging block
-        hipdsp_set_error("hipEventSynchronize failed in hipdsp_tmplplan_set_host");
-        rc = HIPDSP_ERR_HIP;
-    }
-    if (rc != HIPDSP_OK) {
-        delete[] taps;
-        return rc;
-    }
-    TmplTaps *h = plan->host;
+    int rc = hipdsp_template_prepare_host(host_templates, n_templates, rows, cols, normalize, taps.data(), h0, q);
+    if (rc == HIPDSP_OK) rc = hd_stage_host_free(&plan->stage);
+    if (rc != HIPDSP_OK) return rc;
+    TmplTaps *h = (TmplTaps *)plan->stage.host;
     const TmShape s = tm_shape(rows, cols);
     const int old_slots = plan->rows > 0 ? tm_shape(plan->rows, plan->cols).n_slots : 0;
-    memset(h, 0, offsetof(TmplTaps, taps) + sizeof(float) * 16 * (size_t)(s.n_slots > old_slots ? s.n_slots : old_slots));
+    memset(h, 0, tm_used(s.n_slots > old_slots ? s.n_slots : old_slots));
     for (int k = 0; k < n_templates; k++) {
         h->head.h0[k] = h0[k];
         h->head.sq[k] = sqrt(q[k]);
@@ -421,7 +360,6 @@ int hipdsp_tmplplan_set_host(hipdsp_ctx *ctx, hipdsp_tmplplan *plan, const doubl
                     h->taps[((size_t)rows * cb + (size_t)a * w4 + b) * 16 + k] = taps[(size_t)k * m + (size_t)a * cols + cb + b];
         }
     }
-    delete[] taps;
     plan->n_templates = n_templates;
     plan->rows = rows;
     plan->cols = cols;
@@ -433,17 +371,12 @@ int hipdsp_tmplplan_upload(hipdsp_ctx *ctx, hipdsp_tmplplan *plan)
 {
     HD_REQUIRE(ctx != nullptr && plan != nullptr, "NULL argument");
     HD_REQUIRE(plan->n_templates > 0, "plan has no templates yet");
-    const TmShape s = tm_shape(plan->rows, plan->cols);
-    HD_CHECK_HIP(hipMemcpyAsync(plan->dev, plan->host, offsetof(TmplTaps, taps) + sizeof(float) * 16 * (size_t)s.n_slots,
-                                hipMemcpyHostToDevice, ctx->stream));
+    const int rc = hd_stage_upload(ctx, &plan->stage, tm_used(tm_shape(plan->rows, plan->cols).n_slots));
+    if (rc != HIPDSP_OK) return rc;
     plan->up_templates = plan->n_templates;
     plan->up_rows = plan->rows;
     plan->up_cols = plan->cols;
     plan->up_normalize = plan->normalize;
-    if (!hd_capturing(ctx)) {
-        HD_CHECK_HIP(hipEventRecord(plan->uploaded, ctx->stream));
-        plan->valid = true;
-    }
     return HIPDSP_OK;
 }
 
@@ -478,26 +411,16 @@ int hipdsp_template_match(hipdsp_ctx *ctx, const hipdsp_tmplplan *plan, const fl
     HD_REQUIRE(spec_pitch >= 0 && out_pitch >= 0 && out_template_pitch >= 0, "negative pitch");
     HD_REQUIRE(frames <= (1LL << 40), "too many frames");
     if (spec_pitch == 0) spec_pitch = frames * nfreq;
-    if (out_pitch == 0) out_pitch = n_out;
-    if (out_template_pitch == 0) out_template_pitch = channels * out_pitch;
     HD_REQUIRE(spec_pitch >= frames * nfreq, "spec_pitch smaller than one channel");
-    HD_REQUIRE(out_pitch >= n_out, "out_pitch smaller than n_out");
-    if (n_out == 0 || channels == 0) return HIPDSP_OK;
-    HD_REQUIRE(out_template_pitch >= (channels - 1) * out_pitch + n_out, "out_template_pitch smaller than one template's block");
-    HD_REQUIRE(out != nullptr && (spec != nullptr || frames == 0), "NULL data pointer");
-    HD_REQUIRE(channels <= 65535 && n_out <= (1LL << 36), "too many channels or outputs for one call");
+    bool empty;
+    int rc = mb_check_out("template", spec, frames, channels, n_out, out, &out_pitch, &out_template_pitch, &empty);
+    if (rc != HIPDSP_OK || empty) return rc;
     HD_REQUIRE(first >= -(1LL << 60) && first <= (1LL << 60), "first out of range");
-    if (frames > 0) {
-        const char *x0 = (const char *)spec, *x1 = (const char *)(spec + (channels - 1) * spec_pitch + frames * nfreq);
-        const char *o0 = (const char *)out;
-        const char *o1 = (const char *)(out + (nk - 1) * out_template_pitch + (channels - 1) * out_pitch + n_out);
-        HD_REQUIRE(!(x0 < o1 && o0 < x1), "spec and out must not overlap");
-    }
+    HD_REQUIRE(frames == 0 || !mb_out_overlaps(spec, (channels - 1) * spec_pitch + frames * nfreq, out, nk, out_template_pitch,
+                                               channels, out_pitch, n_out), "spec and out must not overlap");
     HD_CHECK_HIP(hipSetDevice(ctx->device));
-    {
-        const int rc = tm_raise_all(ctx);
-        if (rc != HIPDSP_OK) return rc;
-    }
+    rc = tm_raise_all(ctx);
+    if (rc != HIPDSP_OK) return rc;
     const TmShape s = tm_shape(Tt, Fb);
     TmArgs g;
     memset(&g, 0, sizeof(g));
@@ -510,7 +433,7 @@ int hipdsp_template_match(hipdsp_ctx *ctx, const hipdsp_tmplplan *plan, const fl
     g.floor = floor; g.pivot = pivot;
     g.thr = (double)Tt * (double)Fb * (min_std * min_std);
     g.dba = db ? db_args(ref_power, min_power) : db_args(1.0, 0.0);
-    const TmplTaps *dev = plan->dev;
+    const TmplTaps *dev = (const TmplTaps *)plan->stage.dev;
     if (plan->normalize) return tm_launch<true>(ctx, dev, spec, out, g, channels);
     return tm_launch<false>(ctx, dev, spec, out, g, channels);
 }

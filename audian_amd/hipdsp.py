@@ -218,39 +218,58 @@ def _p(x):
     return ctypes.c_void_p(int(x))
 
 
-class SosPlan(_Handle):
-    """Device-resident plan for one SOS table (see hipdsp_sosplan_* in hip_dsp.h)."""
+class _Plan(_Handle):
+    """A device-resident plan behind hipdsp_<_prefix>_create / _set / _set_host / _upload / _destroy (hip_dsp.h).  A
+    subclass names the prefix and turns the arguments of set() and set_host() into the C arguments (_args)."""
 
-    def __init__(self, ctx, sos=None):
+    _prefix = None
+
+    def __init__(self, ctx):
         self.ctx = ctx
         h = ctypes.c_void_p()
-        check(lib.hipdsp_sosplan_create(ctx.handle, ctypes.byref(h)))
+        check(self._c('create')(ctx.handle, ctypes.byref(h)))
         self._h = h
+
+    def _c(self, name):
+        return getattr(lib, f'hipdsp_{self._prefix}_{name}')
+
+    def _set(self, name, *args):
+        """hipdsp_<prefix>_<name> with the C arguments _args() makes of `args`; _args() returns them behind the arrays
+        they point into, which have to live until the call returns."""
+        keep, cargs = self._args(*args)
+        check(self._c(name)(self.ctx.handle, self._h, *cargs))
+        return keep
+
+    def upload(self):
+        check(self._c('upload')(self.ctx.handle, self._h))
+
+    def _destroy(self):
+        self._c('destroy')(self.ctx.handle, self._h)
+
+
+class SosPlan(_Plan):
+    """Device-resident plan for one SOS table (see hipdsp_sosplan_* in hip_dsp.h)."""
+
+    _prefix = 'sosplan'
+
+    def __init__(self, ctx, sos=None):
+        _Plan.__init__(self, ctx)
         self.n_sections = 0
         if sos is not None:
             self.set(sos)
 
     @staticmethod
-    def _table(sos):
+    def _args(sos):
         sos = np.ascontiguousarray(sos, dtype=np.float64)
         if sos.ndim != 2 or sos.shape[1] != 6:
             raise ValueError('sos must be shape (n_sections, 6)')
-        return sos
+        return sos, (ctypes.c_void_p(sos.ctypes.data), len(sos))
 
     def set(self, sos):
-        sos = self._table(sos)
-        check(lib.hipdsp_sosplan_set(self.ctx.handle, self._h, ctypes.c_void_p(sos.ctypes.data),
-                                     len(sos)))
-        self.n_sections = len(sos)
+        self.n_sections = len(self._set('set', sos))
 
     def set_host(self, sos):
-        sos = self._table(sos)
-        check(lib.hipdsp_sosplan_set_host(self.ctx.handle, self._h,
-                                          ctypes.c_void_p(sos.ctypes.data), len(sos)))
-        self.n_sections = len(sos)
-
-    def upload(self):
-        check(lib.hipdsp_sosplan_upload(self.ctx.handle, self._h))
+        self.n_sections = len(self._set('set_host', sos))
 
     def info(self):
         w = ctypes.c_int64()
@@ -258,82 +277,61 @@ class SosPlan(_Handle):
         check(lib.hipdsp_sosplan_info(self.ctx.handle, self._h, ctypes.byref(w), ctypes.byref(e)))
         return int(w.value), int(e.value)
 
-    def _destroy(self):
-        lib.hipdsp_sosplan_destroy(self.ctx.handle, self._h)
 
-
-class FirPlan(_Handle):
+class FirPlan(_Plan):
     """Device-resident taps and thresholds of up to 16 FIR kernels of one length (hipdsp_firplan_* in hip_dsp.h)."""
 
+    _prefix = 'firplan'
+
     def __init__(self, ctx, taps=None, thresholds=None):
-        self.ctx = ctx
-        h = ctypes.c_void_p()
-        check(lib.hipdsp_firplan_create(ctx.handle, ctypes.byref(h)))
-        self._h = h
+        _Plan.__init__(self, ctx)
         self.n_kernels = self.n_taps = 0
         if taps is not None:
             self.set(taps, thresholds)
 
     @staticmethod
-    def _tables(taps, thresholds):
+    def _args(taps, thresholds):
         taps = np.ascontiguousarray(np.atleast_2d(np.asarray(taps, dtype=np.float64)))
         if taps.ndim != 2:
             raise ValueError('taps must be shape (n_kernels, n_taps)')
-        if thresholds is not None:
-            thresholds = np.ascontiguousarray(np.broadcast_to(np.asarray(thresholds, dtype=np.float64), (len(taps),)))
-        return taps, thresholds
-
-    def _call(self, fn, taps, thresholds):
-        taps, thr = self._tables(taps, thresholds)
-        check(fn(self.ctx.handle, self._h, ctypes.c_void_p(taps.ctypes.data), taps.shape[0], taps.shape[1],
-                 ctypes.c_void_p(thr.ctypes.data if thr is not None else 0)))
-        self.n_kernels, self.n_taps = taps.shape
+        thr = thresholds
+        if thr is not None:
+            thr = np.ascontiguousarray(np.broadcast_to(np.asarray(thr, dtype=np.float64), (len(taps),)))
+        return (taps, thr), (ctypes.c_void_p(taps.ctypes.data), taps.shape[0], taps.shape[1],
+                             ctypes.c_void_p(thr.ctypes.data if thr is not None else 0))
 
     def set(self, taps, thresholds=None):
-        self._call(lib.hipdsp_firplan_set, taps, thresholds)
+        self.n_kernels, self.n_taps = self._set('set', taps, thresholds)[0].shape
 
     def set_host(self, taps, thresholds=None):
-        self._call(lib.hipdsp_firplan_set_host, taps, thresholds)
-
-    def upload(self):
-        check(lib.hipdsp_firplan_upload(self.ctx.handle, self._h))
-
-    def _destroy(self):
-        lib.hipdsp_firplan_destroy(self.ctx.handle, self._h)
+        self.n_kernels, self.n_taps = self._set('set_host', taps, thresholds)[0].shape
 
 
-class TmplPlan(_Handle):
+class TmplPlan(_Plan):
     """Device-resident taps of up to 16 spectrogram templates of one shape (Tt frames, Fb bins), raw or normalised
     (hipdsp_tmplplan_* in hip_dsp.h)."""
 
+    _prefix = 'tmplplan'
+
     def __init__(self, ctx, templates=None, normalize=True):
-        self.ctx = ctx
-        h = ctypes.c_void_p()
-        check(lib.hipdsp_tmplplan_create(ctx.handle, ctypes.byref(h)))
-        self._h = h
+        _Plan.__init__(self, ctx)
         self.n_templates = self.rows = self.cols = 0
         self.normalize = bool(normalize)
         if templates is not None:
             self.set(templates, normalize)
 
-    def _call(self, fn, templates, normalize):
+    @staticmethod
+    def _args(templates, normalize):
         t = _templates(templates)
-        check(fn(self.ctx.handle, self._h, ctypes.c_void_p(t.ctypes.data), t.shape[0], t.shape[1], t.shape[2],
-                 int(bool(normalize))))
-        self.n_templates, self.rows, self.cols = t.shape
-        self.normalize = bool(normalize)
+        return t, (ctypes.c_void_p(t.ctypes.data), t.shape[0], t.shape[1], t.shape[2], int(bool(normalize)))
 
     def set(self, templates, normalize=True):
-        self._call(lib.hipdsp_tmplplan_set, templates, normalize)
+        self.n_templates, self.rows, self.cols = self._set('set', templates, normalize).shape
+        self.normalize = bool(normalize)
 
     def set_host(self, templates, normalize=True):
-        self._call(lib.hipdsp_tmplplan_set_host, templates, normalize)
-
-    def upload(self):
-        check(lib.hipdsp_tmplplan_upload(self.ctx.handle, self._h))
-
-    def _destroy(self):
-        lib.hipdsp_tmplplan_destroy(self.ctx.handle, self._h)
+        self.n_templates, self.rows, self.cols = self._set('set_host', templates, normalize).shape
+        self.normalize = bool(normalize)
 
 
 def _templates(templates):

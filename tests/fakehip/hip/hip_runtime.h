@@ -1,6 +1,6 @@
 /* A fake HIP runtime for the CPU sanitizer build of libhip_dsp's HOST-ONLY translation units (ctx.hip: context,
  * stream-ordered block cache, scratch, options; sos_plan.hip: plan mathematics, segment planner; spec_host.hip: frame
- * count, window sum, FFT tables) -- test
+ * count, window sum, FFT tables; the header plan_stage.h: the plans' staged block) -- test
  * infrastructure, tests/test_shim_sanitizers.py.  "Device" memory is host memory, streams and events are small
  * heap objects, everything completes at once; stream capture is a flag per stream so that the block cache's
  * capture rules can be exercised.  Nothing of the product is built against this header. */

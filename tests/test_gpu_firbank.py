@@ -248,6 +248,31 @@ def test_kernels_do_not_depend_on_their_neighbours(L, step):
     plan.close()
 
 
+def test_a_plan_that_shrinks_and_grows_is_a_fresh_plan():
+    """One FirPlan set to the largest bank, the smallest and one in between, thresholds on the first and the last only:
+    after each set the traces, linear and rectified, at step 1 and at step 96, have the bits a newly created plan
+    gives -- no tap or threshold of the bank before is left in the staged block (the host block is cleared up to
+    the larger of the old and new sizes, the upload copies the new prefix over a device block that began as zeros)."""
+    from audian_amd import hipdsp
+    rng = np.random.default_rng(20261021)
+    C, frames = 2, 700
+    x = rng.uniform(-1.0, 1.0, (C, frames)).astype(np.float32)
+    plan = hipdsp.FirPlan(gh.ctx())
+    for K, L, thresholds in ((16, 4097, True), (1, 3, False), (5, 257, True)):
+        taps = rng.standard_normal((K, L))
+        thr = rng.uniform(-0.5, 0.5, K) if thresholds else None
+        plan.set(taps, thr)
+        fresh = hipdsp.FirPlan(gh.ctx(), taps, thr)
+        for step in (1, 96):
+            n_out = -(-frames//step)
+            for rectify in (False, True):
+                got = run(x, plan, 0, step, n_out, rectify=rectify)
+                want = run(x, fresh, 0, step, n_out, rectify=rectify)
+                assert np.array_equal(bits(got), bits(want)), (K, L, step, rectify)
+        fresh.close()
+    plan.close()
+
+
 # ---- 5. non-finite samples --------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize('L, step', [(9, 1), (258, 1), (257, 3), (63, 1000)])

@@ -240,6 +240,28 @@ def test_determinism(normalize, db):
     plan.close()
 
 
+@pytest.mark.parametrize('normalize', [True, False], ids=['normalised', 'raw'])
+def test_a_plan_that_shrinks_and_grows_is_a_fresh_plan(normalize):
+    """One TmplPlan set to a large shape, a tiny one and one in between: after each set the scores have the bits a
+    newly created plan gives -- nothing of the shape before is left in the staged block (the host block is cleared up
+    to the larger of the old and new sizes, the upload copies the new prefix over a device block that began as zeros)."""
+    from audian_amd import hipdsp
+    rng = np.random.default_rng(20261021)
+    C, frames, nfreq = 2, 300, 129
+    spec = rng.uniform(0.1, 1.0, (C, frames, nfreq)).astype(np.float32)
+    plan = hipdsp.TmplPlan(gh.ctx())
+    for K, Tt, Fb in ((16, 32, 128), (1, 3, 5), (4, 100, 20)):
+        tm = rng.standard_normal((K, Tt, Fb))
+        plan.set(tm, normalize)
+        fresh = hipdsp.TmplPlan(gh.ctx(), tm, normalize)
+        got = run(spec, plan, 1, 0, frames - Tt + 1, pivot=0.5)
+        want = run(spec, fresh, 1, 0, frames - Tt + 1, pivot=0.5)
+        assert np.array_equal(bits(got), bits(want)), (K, Tt, Fb)
+        assert np.all(np.isfinite(want)) and len({want[k].tobytes() for k in range(K)}) == K
+        fresh.close()
+    plan.close()
+
+
 # ---- 4. refusals ----------------------------------------------------------------------------------------------------
 
 def test_refusals_leave_out_untouched():

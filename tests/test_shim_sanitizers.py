@@ -2,7 +2,8 @@
 SURVEY 5 asks for it, GPU sanitizers are not available on the pool): ctx.hip (context, options, scratch, the
 stream-ordered block cache behind hipdsp_malloc / hipdsp_free), sos_plan.hip (plan mathematics, segment planner) and
 spec_host.hip (the spectrogram's frame count, window sum and FFT tables, each against its definition restated here)
-are compiled with g++ against a fake HIP runtime (tests/fakehip: host memory, streams and events as heap objects)
+and the header plan_stage.h (the staged block of the device-resident plans: create and its unwinding, destroy, prefix
+uploads, uploads inside a capture) are compiled with g++ against a fake HIP runtime (tests/fakehip: host memory, streams and events as heap objects)
 and driven through the C ABI by a small program; any out-of-bounds access, leak or UB aborts it."""
 
 import os
@@ -19,6 +20,7 @@ DRIVER = r'''
 #include "hip/hip_runtime.h"
 #include "hip_dsp.h"
 #include "common.h"
+#include "plan_stage.h"
 size_t fake_hip_limit = 0, fake_hip_in_use = 0;
 int fake_hip_fail_event_create = 0;
 long fake_hip_waits = 0;
@@ -120,6 +122,50 @@ int main()
         }
         const double got = hd_hann_sumsq(nfft);
         EXPECT(memcmp(&got, &wss, sizeof(wss)) == 0);
+    }
+    // ---- the staged block of the device-resident plans (plan_stage.h), on a stream of its own: nothing else holds
+    // "device" memory yet
+    {
+        fake_stream st = {0};
+        hipdsp_ctx sc;
+        memset(&sc, 0, sizeof(sc));
+        sc.stream = &st;
+        const size_t N = 4096;
+        hd_plan_stage s;
+        CHECK(hd_stage_create(&sc, &s, N, false));
+        EXPECT(s.host && s.dev && s.uploaded && s.bytes == N && !s.valid && fake_hip_in_use == N);
+        for (size_t i = 0; i < N; i++) EXPECT(((unsigned char *)s.host)[i] == 0);
+        hd_stage_destroy(&sc, &s);
+        EXPECT(fake_hip_in_use == 0 && s.host == nullptr && s.dev == nullptr && s.uploaded == nullptr);
+        hd_stage_destroy(&sc, &s);                                  // of a destroyed one, and of none
+        hd_stage_destroy(&sc, nullptr);
+        // a step that fails frees what the steps before it made (the pinned block: the leak check at exit)
+        fake_hip_fail_event_create = 1;
+        EXPECT(hd_stage_create(&sc, &s, N, true) == HIPDSP_ERR_HIP);
+        EXPECT(fake_hip_fail_event_create == 0 && fake_hip_in_use == 0 && s.host == nullptr && s.dev == nullptr);
+        fake_hip_limit = N - 1;
+        EXPECT(hd_stage_create(&sc, &s, N, true) == HIPDSP_ERR_HIP);
+        fake_hip_limit = 0;
+        EXPECT(fake_hip_in_use == 0 && s.host == nullptr && s.uploaded == nullptr);
+        // an upload copies exactly the prefix it is asked for; inside a capture it records nothing
+        CHECK(hd_stage_create(&sc, &s, N, true));
+        unsigned char *h = (unsigned char *)s.host, *d = (unsigned char *)s.dev;
+        for (size_t i = 0; i < N; i++) h[i] = (unsigned char)(1 + i % 251);
+        CHECK(hd_stage_host_free(&s));                              // nothing to wait for yet
+        st.capturing = 1;
+        CHECK(hd_stage_upload(&sc, &s, 100));
+        EXPECT(!s.valid && !s.uploaded->recorded);
+        st.capturing = 0;
+        for (size_t i = 0; i < N; i++) EXPECT(d[i] == (i < 100 ? h[i] : 0));
+        CHECK(hd_stage_upload(&sc, &s, 1000));
+        EXPECT(s.valid && s.uploaded->recorded && s.uploaded->on == &st);
+        for (size_t i = 0; i < N; i++) EXPECT(d[i] == (i < 1000 ? h[i] : 0));
+        CHECK(hd_stage_host_free(&s));
+        CHECK(hd_stage_upload(&sc, &s, N));
+        EXPECT(memcmp(d, h, N) == 0);
+        EXPECT(hd_stage_upload(&sc, &s, N + 1) == HIPDSP_ERR_INVALID);
+        hd_stage_destroy(&sc, &s);
+        EXPECT(fake_hip_in_use == 0);
     }
     // ---- context, options, scratch, block cache
     hipdsp_ctx *ctx = nullptr;
