@@ -96,7 +96,7 @@ __global__ __launch_bounds__(128 * NP, NP / 2) void chain_bwd_kernel(const SosPl
         bool pre = false;
         auto fetch = [&](long long tidx) {
 #pragma unroll
-            for (int k = 0; k < 8; k++) nx[k] = asm_load16(in + tidx * TILE + 256 * k + 4 * lane);
+            for (int k = 0; k < 8; k++) nx[k] = asm_load16_stream<HD_NT_YF_LD>(in + tidx * TILE + 256 * k + 4 * lane);
 #pragma unroll
             for (int i = 0; i < SE; i++) nck[i] = asm_load16(ckpt + tidx * DE + 2 * i);
         };
@@ -242,7 +242,7 @@ __global__ __launch_bounds__(128 * NP, NP / 2) void chain_bwd_kernel(const SosPl
                             v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
                         }
                         f4u t; t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w;
-                        *reinterpret_cast<f4u *>(out + (tile + 256 * k + 4 * lane)) = t;
+                        store_stream<HD_NT_ENV>(reinterpret_cast<f4u *>(out + (tile + 256 * k + 4 * lane)), t);
                     }
                     asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
                 } else {

@@ -332,7 +332,7 @@ __device__ __forceinline__ void psd_frame_core(float2 *v, const float corr, floa
     bo_k &= 0xfffc; bo_m &= 0xfffc;
     const int soff = out.soff;
     auto st_bin = [soff](__amdgpu_buffer_rsrc_t r, int boff, int imm, float val) {
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(val), r, boff + imm, soff, 0);
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(val), r, boff + imm, soff, HD_POL_AUX(HD_NT_PSD));
     };
     float pk_last = 0.f;
     const v2f hscale2 = {scale.half, scale.half};
@@ -565,7 +565,7 @@ __global__ __launch_bounds__(128 * NP, NP / 2) void chain_fwd_kernel(const SosPl
         const int top_full_t = TT - 1;                               // host guarantees >= 0
         auto fetch = [&](int t0) {
 #pragma unroll
-            for (int k = 0; k < 8; k++) nx[k] = asm_load16(in + (long long)t0 * TILE + 256 * k + 4 * lane);
+            for (int k = 0; k < 8; k++) nx[k] = asm_load16_stream<HD_NT_X>(in + (long long)t0 * TILE + 256 * k + 4 * lane);
         };
         // what iteration k + 1 will read: its tile if that is a full tile of this unit, else a dummy
         auto prefetchable = [&](int t0) { return t0 >= start_t && t0 < end_t && t0 < TT && t0 >= lead_t; };
@@ -692,7 +692,7 @@ __global__ __launch_bounds__(128 * NP, NP / 2) void chain_fwd_kernel(const SosPl
                 for (int k = 0; k < 8; k++) {
                     const float4 v = lds[lds_slot(8 * k + (lane >> 3), lane & 7)];
                     f4u t; t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w;
-                    *reinterpret_cast<f4u *>(yf + (long long)tt * TILE + 256 * k + 4 * lane) = t;
+                    store_stream<HD_NT_YF_ST>(reinterpret_cast<f4u *>(yf + (long long)tt * TILE + 256 * k + 4 * lane), t);
                 }
                 asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
                 STAMP_AT(4);                                   // H1, 8 stores of the filtered tile, wait for the prefetch
@@ -936,7 +936,7 @@ __global__ __launch_bounds__(128 * NP, NP / 2) void chain_fwd_kernel(const SosPl
 #pragma unroll
                     for (int j = 0; j < 16; j++) {             // (x and yf are shifted by -lead: 4-byte alignment only)
                         f2u t; t.x = cur_[j].x; t.y = cur_[j].y;
-                        *reinterpret_cast<f2u *>(dst + 128 * j) = t;
+                        store_stream<HD_NT_YF_ST>(reinterpret_cast<f2u *>(dst + 128 * j), t);
                     }
                 }
             }

@@ -162,7 +162,7 @@ __global__ __launch_bounds__(64 * WPB) void sos_ckpt_kernel(const SosPlanDev *__
     const long long top_full = (T / TILE - 1) * TILE;            // host guarantees >= 0
     auto fetch = [&](long long t0) {
 #pragma unroll
-        for (int k = 0; k < 8; k++) nx[k] = asm_load16(in + t0 + 256 * k + 4 * lane);
+        for (int k = 0; k < 8; k++) nx[k] = asm_load16_stream<HD_NT_X>(in + t0 + 256 * k + 4 * lane);
     };
     if (PREFETCH) {
         pre = start < loop_end && start + TILE <= T && start >= lead;
@@ -226,7 +226,7 @@ __global__ __launch_bounds__(64 * WPB) void sos_ckpt_kernel(const SosPlanDev *__
                     for (int k = 0; k < 8; k++) {
                         const v4f v = rows[k];
                         f4u t; t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w;
-                        *reinterpret_cast<f4u *>(yf + tile + 256 * k + 4 * lane) = t;
+                        store_stream<HD_NT_YF_ST>(reinterpret_cast<f4u *>(yf + tile + 256 * k + 4 * lane), t);
                     }
                     if (PREFETCH) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
                 } else {
@@ -539,7 +539,7 @@ __global__ __launch_bounds__(64 * WPB, REGW ? 2 : 1) void env_bwd_kernel(const S
     bool pre = false;
     auto fetch = [&](long long tidx) {
 #pragma unroll
-        for (int k = 0; k < 8; k++) nx[k] = asm_load16(in + tidx * TILE + 256 * k + 4 * lane);
+        for (int k = 0; k < 8; k++) nx[k] = asm_load16_stream<HD_NT_YF_LD>(in + tidx * TILE + 256 * k + 4 * lane);
 #pragma unroll
         for (int i = 0; i < SE; i++) nck[i] = asm_load16(ckpt + tidx * DE + 2 * i);
     };
@@ -751,14 +751,14 @@ __global__ __launch_bounds__(64 * WPB, REGW ? 2 : 1) void env_bwd_kernel(const S
                     for (int k = 0; k < 8; k++) {
                         const v4f v = rows[k];
                         f4u t; t.x = max_zero(v.x); t.y = max_zero(v.y); t.z = max_zero(v.z); t.w = max_zero(v.w);
-                        *reinterpret_cast<f4u *>(out + (tile + 256 * k + 4 * lane - a.skip)) = t;
+                        store_stream<HD_NT_ENV>(reinterpret_cast<f4u *>(out + (tile + 256 * k + 4 * lane - a.skip)), t);
                     }
                 } else {
 #pragma unroll
                     for (int k = 0; k < 8; k++) {
                         const v4f v = rows[k];
                         f4u t; t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w;
-                        *reinterpret_cast<f4u *>(out + (tile + 256 * k + 4 * lane - a.skip)) = t;
+                        store_stream<HD_NT_ENV>(reinterpret_cast<f4u *>(out + (tile + 256 * k + 4 * lane - a.skip)), t);
                     }
                 }
                 // the prefetch issued above is older than these 8 stores: all but 7 operations done

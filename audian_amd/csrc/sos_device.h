@@ -263,6 +263,92 @@ __device__ __forceinline__ v4f asm_load16(const void *p)
     asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(r) : "v"(p) : "memory");
     return r;
 }
+
+// ---- streaming accesses ----------------------------------------------------------------------------------
+// Every byte of the big streams of a sweep -- x, yf, the PSD / dB rows, env -- is touched once per launch.  This is the
+// one place that spells such an access with a cache policy, chosen per stream at BUILD time:
+//   HD_POL_DEFAULT  the plain instruction;
+//   HD_POL_NT       the `nt` bit: a load is served by the L2 past the CU's L1, a store's line stays in the L2;
+//   HD_POL_SC1_NT   `sc1 nt`: the load as above, the store also drops its line from the L2 once written through.
+// A policy changes no value and no instruction count: a hinted load is the same untracked asm load with a suffix, a
+// hinted store is one vector-memory instruction like the plain one (the counted waits of the prefetches, DESIGN 5.1b,
+// depend on that).  Tile states, plan tables and the clamped border-tile paths stay on the default policy: they are small
+// and read again.
+//   -DHD_NT_X=p      loads of x           chain_fwd_kernel, sos_ckpt_kernel
+//   -DHD_NT_YF_ST=p  stores of yf         the same two, FFT-wave and IIR-wave path
+//   -DHD_NT_PSD=p    PSD and dB stores    BinSink
+//   -DHD_NT_YF_LD=p  loads of yf          env_bwd_kernel, chain_bwd_kernel
+//   -DHD_NT_ENV=p    stores of env        the same two
+// (make HINTS="-DHD_NT_X=1 ..." for an A/B; -DHD_STREAM_HINTS_OFF: every stream on the default policy, whatever else is
+// set -- the build the bit-identity test compares against.)  The defaults below are the streams that won their A/B
+// (profiles/r08_stream_hints_ab.log): nt on the four traces, -0.6 ... -2.1 % of their launch each; the PSD rows lose 1.6 %
+// with nt and 4.7 % with sc1 nt (4-byte stores per lane, unlike the traces' 16) and stay plain.
+#define HD_POL_DEFAULT 0
+#define HD_POL_NT 1
+#define HD_POL_SC1_NT 2
+#ifdef HD_STREAM_HINTS_OFF
+#undef HD_NT_X
+#undef HD_NT_YF_ST
+#undef HD_NT_PSD
+#undef HD_NT_YF_LD
+#undef HD_NT_ENV
+#define HD_NT_X HD_POL_DEFAULT
+#define HD_NT_YF_ST HD_POL_DEFAULT
+#define HD_NT_PSD HD_POL_DEFAULT
+#define HD_NT_YF_LD HD_POL_DEFAULT
+#define HD_NT_ENV HD_POL_DEFAULT
+#endif
+#ifndef HD_NT_X
+#define HD_NT_X HD_POL_NT
+#endif
+#ifndef HD_NT_YF_ST
+#define HD_NT_YF_ST HD_POL_NT
+#endif
+#ifndef HD_NT_PSD
+#define HD_NT_PSD HD_POL_DEFAULT
+#endif
+#ifndef HD_NT_YF_LD
+#define HD_NT_YF_LD HD_POL_NT
+#endif
+#ifndef HD_NT_ENV
+#define HD_NT_ENV HD_POL_NT
+#endif
+// the `aux` operand of the raw buffer store builtins for a policy (gfx950: bit 1 = nt, bit 4 = sc1)
+#define HD_POL_AUX(pol) ((pol) == HD_POL_NT ? 2 : ((pol) == HD_POL_SC1_NT ? 18 : 0))
+
+// the untracked 16-byte prefetch load of a streamed trace
+template <int POL>
+__device__ __forceinline__ v4f asm_load16_stream(const void *p)
+{
+    static_assert(POL >= HD_POL_DEFAULT && POL <= HD_POL_SC1_NT, "unknown cache policy");
+    v4f r;
+    if constexpr (POL == HD_POL_NT) asm volatile("global_load_dwordx4 %0, %1, off nt" : "=v"(r) : "v"(p) : "memory");
+    else if constexpr (POL == HD_POL_SC1_NT) asm volatile("global_load_dwordx4 %0, %1, off sc1 nt" : "=v"(r) : "v"(p) : "memory");
+    else return asm_load16(p);
+    return r;
+}
+
+// A store of a streamed trace: an f4u (16 bytes) or f2u (8) at dst.  Default and nt are stores hipcc sees (it folds the row's
+// constant into the instruction's offset field as before); `sc1 nt` has no builtin and is the asm form, its address whole
+// in the register pair.  Either way one vector-memory instruction.
+// (one overload per width, not a template over the vector type: a deduced type loses f4u's 4-byte alignment)
+template <int POL>
+__device__ __forceinline__ void store_stream(f4u *dst, const f4u t)
+{
+    static_assert(POL >= HD_POL_DEFAULT && POL <= HD_POL_SC1_NT, "unknown cache policy");
+    if constexpr (POL == HD_POL_NT) __builtin_nontemporal_store(t, dst);
+    else if constexpr (POL == HD_POL_SC1_NT) asm volatile("global_store_dwordx4 %0, %1, off sc1 nt" ::"v"(dst), "v"(t) : "memory");
+    else *dst = t;
+}
+template <int POL>
+__device__ __forceinline__ void store_stream(f2u *dst, const f2u t)
+{
+    static_assert(POL >= HD_POL_DEFAULT && POL <= HD_POL_SC1_NT, "unknown cache policy");
+    if constexpr (POL == HD_POL_NT) __builtin_nontemporal_store(t, dst);
+    else if constexpr (POL == HD_POL_SC1_NT) asm volatile("global_store_dwordx2 %0, %1, off sc1 nt" ::"v"(dst), "v"(t) : "memory");
+    else *dst = t;
+}
+
 __device__ __forceinline__ float asm_load4(const float *p)
 {
     float r;
