@@ -11,7 +11,9 @@ __version__ = '0.1.0'
 
 # names resolved on first use, so that importing the package stays free of side effects
 _EXPORTS = {'NoiseProfile': 'noiseprofile', 'host_bin_quantiles': 'noiseprofile', 'host_equalize': 'noiseprofile',
-            'BufferedEqualizedSpectrogram': 'bufferedequalizedspectrogram'}
+            'BufferedEqualizedSpectrogram': 'bufferedequalizedspectrogram',
+            'BufferedAdaptiveSpectrogram': 'bufferedadaptivespectrogram', 'host_adapt': 'bufferedadaptivespectrogram',
+            'smooth_for': 'bufferedadaptivespectrogram'}
 __all__ = sorted(_EXPORTS)
 
 

@@ -140,6 +140,7 @@ _SIGNATURES = {
     'hipdsp_spectral_features': ([_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, ctypes.c_uint, _dbl, _dbl, _dbl, _vp, _i64, _i64], _int),
     'hipdsp_bin_quantiles': ([_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _dbl, _vp, _vp], _int),
     'hipdsp_spec_equalize': ([_vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _int], _int),
+    'hipdsp_spec_adapt': ([_vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _dbl, _int, _dbl, _dbl, _dbl, _dbl], _int),
     'hipdsp_firplan_create': ([_vp, _pp], _int),
     'hipdsp_firplan_destroy': ([_vp, _vp], _int),
     'hipdsp_firplan_set': ([_vp, _vp, _vp, _int, _int, _vp], _int),

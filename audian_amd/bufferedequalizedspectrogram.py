@@ -16,7 +16,60 @@ from .bufferedspectrogram import BufferedSpectrogram
 from .noiseprofile import MODES, NoiseProfile, host_equalize
 
 
-class BufferedEqualizedSpectrogram(BufferedSpectrogram):
+class BufferedFollowingSpectrogram(BufferedSpectrogram):
+    """A spectrogram-shaped trace computed from a spectrogram-shaped SOURCE, one frame per source frame: it takes over the
+    source's window, hop, frequency axis and sample rate at open() and at every recompute(), its buffer lies exactly over
+    the source's, set_hop() is not its to call and the fused forward sweep never writes it.  The base of
+    BufferedEqualizedSpectrogram and BufferedAdaptiveSpectrogram."""
+
+    def __init__(self, name, source, panel='spectrogram'):
+        BufferedSpectrogram.__init__(self, name, source, panel=panel)
+        # window and hop are the source's from open() on (set_hop() is not this trace's to call), and a frame needs
+        # nothing of its source but the same frame: none of the spectrogram's margin
+        self.hop = 128
+        self.source_tbefore = self.source_tafter = 0
+
+    def _follow(self):
+        """Take over the source's window, hop and frequency axis."""
+        src = self.source
+        self.nfft, self.hop, self.overlap_frac = src.nfft, src.hop, src.overlap_frac
+        self.fresolution, self.tresolution = src.fresolution, src.tresolution
+        self.frequencies = src.frequencies
+        self.ampl_min, self.ampl_max = src.ampl_min, src.ampl_max
+
+    @property
+    def sample_rate(self):
+        return self.source.sample_rate
+
+    def _recording_samples(self):
+        return self.source._recording_samples()
+
+    def _open_following(self, source):
+        if len(getattr(source, 'shape', ())) != 3 or not hasattr(source, 'nfft'):
+            raise ValueError(f'{self.name}: the source must be a spectrogram (frames, channels, bins)')
+        BufferedData.open(self, source, 1, more_shape=(int(source.shape[2]),))
+        self._follow()
+        self.spec_rect, self.use_spec = [], True
+
+    def _follow_geometry(self):
+        """The source's current geometry: one frame per source frame, the buffer exactly over the source's."""
+        src = self.source
+        self.update_step(1, more_shape=(int(src.shape[2]),))
+        self.offset, self.bufferframes = src.offset, self._source_len()
+        self._follow()
+
+    def _fusable_with(self, filt):
+        return None              # the fused forward sweep writes spectrograms of the filtered trace, never this one
+
+    def set_hop(self):
+        return False
+
+    def _set_spec_rect(self):
+        self.spec_rect = [self.offset/self.rate, 0, len(self._hostbuf)/self.rate,
+                          getattr(self.source, 'ampl_max', 0) + self.fresolution]
+
+
+class BufferedEqualizedSpectrogram(BufferedFollowingSpectrogram):
     """``source / profile`` (`mode` 'divide') or ``max(source - profile, 0)`` ('subtract') in float32, frame by frame:
     shape (frames, channels, bins) and step of the source.  `profile` is a noiseprofile.NoiseProfile
     (BufferedSpectrogram.noise_profile, TraceGraph.estimate_noise_profile); with None the trace is a copy of its source.
@@ -28,11 +81,7 @@ class BufferedEqualizedSpectrogram(BufferedSpectrogram):
     profile stale, the trace fills with NaN and `stale` is True until a fitting profile (or None) is set."""
 
     def __init__(self, name='equalized', source='spectrogram', panel='spectrogram', mode='divide', profile=None):
-        BufferedSpectrogram.__init__(self, name, source, panel=panel)
-        # window and hop are the source's from open() on (set_hop() is not this trace's to call), and a frame needs
-        # nothing of its source but the same frame: none of the spectrogram's margin
-        self.hop = 128
-        self.source_tbefore = self.source_tafter = 0
+        BufferedFollowingSpectrogram.__init__(self, name, source, panel=panel)
         self.mode = self._checked_mode(mode)
         self.profile = self._checked(profile)
         self.stale = False
@@ -58,40 +107,16 @@ class BufferedEqualizedSpectrogram(BufferedSpectrogram):
                              f'{profile.fresolution!r} Hz) does not fit {source.name} ({source.channels} x '
                              f'{int(source.shape[2])} of {float(source.fresolution)!r} Hz)')
 
-    def _follow(self):
-        """Take over the source's window, hop and frequency axis."""
-        src = self.source
-        self.nfft, self.hop, self.overlap_frac = src.nfft, src.hop, src.overlap_frac
-        self.fresolution, self.tresolution = src.fresolution, src.tresolution
-        self.frequencies = src.frequencies
-        self.ampl_min, self.ampl_max = src.ampl_min, src.ampl_max
-
-    @property
-    def sample_rate(self):
-        return self.source.sample_rate
-
-    def _recording_samples(self):
-        return self.source._recording_samples()
-
     def open(self, source):
-        if len(getattr(source, 'shape', ())) != 3 or not hasattr(source, 'nfft'):
-            raise ValueError(f'{self.name}: the source must be a spectrogram (frames, channels, bins)')
-        self._require_fit(self.profile, source)
-        BufferedData.open(self, source, 1, more_shape=(int(source.shape[2]),))
-        self._follow()
-        self.spec_rect, self.use_spec = [], True
+        if len(getattr(source, 'shape', ())) == 3 and hasattr(source, 'nfft'):
+            self._require_fit(self.profile, source)
+        self._open_following(source)
         self._set_unit()
         self.stale = False
 
     def _set_unit(self):
         src = self.source
         self.unit = '' if self.mode == 'divide' and self.profile is not None else src.unit
-
-    def _fusable_with(self, filt):
-        return None              # the fused forward sweep writes spectrograms of the filtered trace, never this one
-
-    def set_hop(self):
-        return False
 
     def set_profile(self, profile):
         """Another profile (None: none, the trace copies its source): recomputes this trace and what hangs below it,
@@ -117,10 +142,7 @@ class BufferedEqualizedSpectrogram(BufferedSpectrogram):
     def recompute(self):
         """Take over the source's current geometry (one frame per source frame, the buffer exactly over the source's),
         see whether the profile still fits, then allocate and compute as the base class does."""
-        src = self.source
-        self.update_step(1, more_shape=(int(src.shape[2]),))
-        self.offset, self.bufferframes = src.offset, self._source_len()
-        self._follow()
+        self._follow_geometry()
         self.stale = self.profile is not None and not self.profile.fits(self)
         BufferedData.recompute(self)
 
@@ -151,8 +173,7 @@ class BufferedEqualizedSpectrogram(BufferedSpectrogram):
         call = self._take_call(source, dest)
         if n > 0:
             self._equalize(source, dest, nbefore, n, call)
-        self.spec_rect = [self.offset/self.rate, 0, len(self._hostbuf)/self.rate,
-                          getattr(self.source, 'ampl_max', 0) + self.fresolution]
+        self._set_spec_rect()
 
     def _equalize(self, source, dest, nbefore, n, call):
         if self.stale:

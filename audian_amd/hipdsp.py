@@ -715,6 +715,36 @@ def spec_equalize(ctx, spec, spec_pitch, out, out_pitch, channels, frames, nfreq
                                    int(frames), int(nfreq), _p(profile), int(profile_pitch), eq_mode(mode)))
 
 
+ADAPT_MODES = {'background': 0, 'divide': 1, 'subtract': 2, 'pcen': 3}          # HIPDSP_ADAPT_ in include/hip_dsp.h
+ADAPT_CHUNK = 256                                                               # HIPDSP_ADAPT_CHUNK
+
+
+def adapt_mode(mode):
+    """HIPDSP_ADAPT_BACKGROUND ... HIPDSP_ADAPT_PCEN of the mode's name (or of the number itself); ValueError else."""
+    if mode in ADAPT_MODES:
+        return ADAPT_MODES[mode]
+    if mode in (0, 1, 2, 3) and not isinstance(mode, bool):
+        return int(mode)
+    raise ValueError(f'unknown adaptive mode {mode!r}: one of {", ".join(ADAPT_MODES)}')
+
+
+def adapt_scratch_bytes(channels, frames, nfreq):
+    """The context scratch one spec_adapt call of these sizes uses (Context.reserve() it before a capture)."""
+    return 8*int(channels)*max(-(-int(frames)//ADAPT_CHUNK) - 1, 0)*int(nfreq)
+
+
+def spec_adapt(ctx, spec, spec_pitch, out, out_pitch, channels, frames, nfreq, nbefore, smooth, mode='pcen', gain=0.98,
+               bias=2.0, power=0.5, eps=1e-20):
+    """out[c, i, k] = the spectrogram slab spec[c, nbefore + i, k] normalised by its running noise floor M (M_0 = x_0,
+    M_t = (1 - smooth) M_(t-1) + smooth x_t along time, per channel and bin): M itself ('background'), x/(eps + M)
+    ('divide'), max(x - M, 0) ('subtract') or (x/(eps + M)**gain + bias)**power - bias**power ('pcen'), float64 rounded
+    once to float32 (hipdsp_spec_adapt); out may be spec itself when nbefore is 0."""
+    _count('spec_adapt')
+    check(lib.hipdsp_spec_adapt(ctx.handle, _p(spec), int(spec_pitch), _p(out), int(out_pitch), int(channels),
+                                int(frames), int(nfreq), int(nbefore), float(smooth), adapt_mode(mode), float(gain),
+                                float(bias), float(power), float(eps)))
+
+
 def fir_bank(ctx, plan, x, x_pitch, channels, frames, first, step, n_out, out, rectify=False, out_pitch=0,
              out_kernel_pitch=0):
     """out[k, c, i] = sum_j taps[k, j] * x[c, first + i*step + (L-1)//2 - j] for every kernel of `plan`, x zero outside

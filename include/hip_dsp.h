@@ -676,6 +676,50 @@ int hipdsp_spec_equalize(hipdsp_ctx *ctx, const float *spec, int64_t spec_pitch,
                          int64_t channels, int64_t frames, int64_t nfreq, const float *profile, int64_t profile_pitch,
                          int mode);
 
+/* Adaptive normalisation of a spectrogram slab: a RUNNING noise floor per channel and bin, and the slab normalised by
+ * it -- for backgrounds that are not stationary (wind, rain, a passing car, a chorus that swells), where the one
+ * profile of hipdsp_spec_equalize is either raised by them or lies below them.  For one column (channel c, bin k) with
+ * x_t = spec[c, t, k], s = smooth, a = 1 - s (one double subtraction):
+ *   M_0 = x_0,   M_t = a*M_(t-1) + s*x_t   (t >= 1)
+ * (scipy.signal.lfilter([s], [1, s-1], x, zi=lfilter_zi(...)*x[0]), the smoother of librosa's pcen).  The first
+ * nbefore rows are warm-up only; output row i belongs to t = nbefore + i, out[c, i, k] = float32(...) of
+ *   HIPDSP_ADAPT_BACKGROUND   M_t                                               the floor itself
+ *   HIPDSP_ADAPT_DIVIDE       x_t / (eps + M_t)
+ *   HIPDSP_ADAPT_SUBTRACT     max(x_t - M_t, 0)
+ *   HIPDSP_ADAPT_PCEN         (x_t / (eps + M_t)**gain + bias)**power - bias**power
+ * evaluated in float64 (state, hand-over and the mode's formula; pow() of the device library twice per element in
+ * PCEN) and rounded to float32 once.  0 < smooth <= 1; eps > 0 for DIVIDE and PCEN (the spectrogram's zero tail
+ * frames give 0, not 0/0); 0 <= gain <= 1, bias >= 0, power > 0 for PCEN (the logarithmic power -> 0 variant is not
+ * served); parameters a mode does not use are not looked at.  A NaN or an infinity at (c, t0, k) gives from t0 on, in
+ * that column alone, the NaN / +inf / -inf / finite pattern of the sequential float64 evaluation of these formulas.
+ * spec holds `frames` rows per channel, out holds frames - nbefore; spec_pitch / out_pitch are elements between
+ * channels (0 = dense: frames*nfreq and (frames - nbefore)*nfreq).  In place (out == spec, equal pitch) is allowed with
+ * nbefore == 0; any other overlap of out with spec is HIPDSP_ERR_INVALID, as are a NULL ctx, NULL pointers with work to
+ * do, a pointer off the 4-byte grid, negative sizes, nbefore > frames, a pitch too small, frames*nfreq or a pitch
+ * beyond 2^44 elements, an unknown mode and parameters outside the ranges above (NaN included); more than 65535
+ * channels is HIPDSP_ERR_UNSUPPORTED.  A refused call writes nothing; channels, nfreq == 0 or nbefore == frames writes
+ * nothing.
+ * Time is cut into chunks of HIPDSP_ADAPT_CHUNK frames counted from row 0 -- a function of `frames` alone, never of
+ * channels, nfreq, the pitches or the device -- with an exact hand-over M' = a^CHUNK*M + v (a^CHUNK from the host,
+ * long double, rounded once; v the chunk's end value from zero state), three launches ordered by the stream: the
+ * summaries v, the scan of the carries, the result (a call of one chunk is the last launch alone).  256 frames: the
+ * carries are 1/128 of the slab's bytes and a 56250-frame slab still gives every CU hundreds of waves.
+ * Promises: no kernel waits for another workgroup, no atomics; all scalars travel by value, the call is up to three
+ * kernel nodes inside hipdsp_graph_begin/end; it uses the context scratch (8 bytes per channel, bin and chunk but the
+ * last), which cannot grow during a capture or next to captured graphs of the context (HIPDSP_ERR_INVALID then):
+ * hipdsp_ctx_reserve() it before; the same call gives the same bits twice and nothing depends on what the scratch
+ * held; a column's bytes depend on that column, nbefore and the parameters alone, not on the other channels or bins of
+ * the call or the pitches; 64-bit index arithmetic, rows at any 4-byte address (dword accesses); the slab is read
+ * twice (less its last chunk and, the second time, the chunks in front of nbefore) and written once. */
+#define HIPDSP_ADAPT_BACKGROUND 0
+#define HIPDSP_ADAPT_DIVIDE 1
+#define HIPDSP_ADAPT_SUBTRACT 2
+#define HIPDSP_ADAPT_PCEN 3
+#define HIPDSP_ADAPT_CHUNK 256
+int hipdsp_spec_adapt(hipdsp_ctx *ctx, const float *spec, int64_t spec_pitch, float *out, int64_t out_pitch,
+                      int64_t channels, int64_t frames, int64_t nfreq, int64_t nbefore, double smooth, int mode,
+                      double gain, double bias, double power, double eps);
+
 /* ---- FIR kernel bank ("feature expansion (kernel filter)") ----------------- */
 
 /* A plan holds, in device memory, the taps and thresholds of up to 16 FIR kernels of one common length, as

@@ -187,6 +187,12 @@ for b in builds:
     logs[b['name']].append(f'{"hipdsp_spec_equalize over the PSD 2048/1024, divide, out of place":78s} {ms:8.3f} ms {8.0*C*nd*F/ms/1e6:7.0f} GB/s')
     if b is builds[-1]:
         print(logs[b['name']][-1], flush=True)
+    if hasattr(h.lib, 'hipdsp_spec_adapt'):            # (tools/adaptive_spectrogram_bench.py has the other modes and the slab copy)
+        ms = min(timed(b, lambda: h.spec_adapt(ctx, ds, 0, out, 0, C, nd, F, 0, 0.0263, 'pcen'), 3) for _ in range(rounds))
+        ctx.synchronize()
+        logs[b['name']].append(f'{"hipdsp_spec_adapt over the PSD 2048/1024, pcen, out of place (two reads, one write)":78s} {ms:8.3f} ms {12.0*C*nd*F/ms/1e6:7.0f} GB/s')
+        if b is builds[-1]:
+            print(logs[b['name']][-1], flush=True)
     for d in (lo_hi, count, prof):
         d.free()
 # ---- hipdsp_fir_bank: 16 kernels of 257 taps over the envelope, one frame per millisecond (tools/fir_bank_bench.py has the
