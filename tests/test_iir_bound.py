@@ -147,26 +147,61 @@ def test_a_float32_tile_between_the_passes_needs_its_term(case):
     print('%s: float32 between the passes %.3f roundings, %.3f beyond the term' % (case, plain, worst))
 
 
-PAIRS = sorted(set(ib.SOSFILT_ENVELOPE) | set(ib.CHAIN.values()) | set(ib.SPLIT_FRAMES))
+PAIRS = sorted(set(ib.SOSFILT_ENVELOPE) | set(ib.CHAIN.values()) | set(ib.SPLIT_FRAMES) | set(ib.MATRIX_PAIRS))
 
 
 @pytest.mark.parametrize('bp,env', PAIRS)
 def test_fused_pairs(bp, env):
     """The envelope of a band-pass output rounded to float32 (the float64 run stands in for the launch's own), from
-    sample 0 and from ENV_FIRST[1], where the kernels form the left extension in float32 too."""
+    sample 0 and from ENV_FIRST[1], where the kernels form the left extension in float32 too.  An envelope of three or
+    four sections runs behind a band-pass through env_bwd_kernel without the register window: that model, with the
+    forward pass rounded to float32 between the passes, misses the bound as it stands and meets it with between_term."""
     sos, rate, fams = ib.design(bp)
     esos, _, efams = ib.design(env, ib.ENVELOPES)
     hp = ib.has_highpass(esos)
     x = ib.families(fams, ib.T_LONG, rate)
     yf = ib.sosfilt_runs(sos, x)[1].astype(np.float32)[:, ib.envelope_lanes(fams, efams)]
-    firsts = ib.ENV_FIRST if (bp, env) in ib.SOSFILT_ENVELOPE or (bp, env) == ib.CHAIN[2048, 1024] else ib.ENV_FIRST[:1]
-    for first in firsts:
+    shifted = (bp, env) in ib.SOSFILT_ENVELOPE or (bp, env) == ib.CHAIN[2048, 1024] or (bp, env) in ib.MATRIX_SHIFTED
+    for first in ib.ENV_FIRST if shifted else ib.ENV_FIRST[:1]:
         what = '%s + %s from %d' % (bp, env, first)
         ref, run = ib.envelope_runs(esos, yf[first:])
         q = check_case(ref, run, what)
         model = ib.sosfiltfilt(esos, yf[first:], np.float64, clamp=False, right_ext_f32=True, left_ext_f32=first > 0)
         term = ib.extension_term(esos, yf[first:], left=first > 0) if hp else None
         ib.assert_within(model.astype(np.float32), ref, q, what + ', float32 extensions', margin=1.0, term=term)
+        if len(esos) > 2:
+            model = ib.sosfiltfilt(esos, yf[first:], np.float64, clamp=False, right_ext_f32=True, left_ext_f32=first > 0,
+                                   between_f32=True).astype(np.float32)
+            with pytest.raises(AssertionError):
+                ib.assert_within(model, ref, q, what)
+            term = ib.between_term(esos, yf[first:]) + (0.0 if term is None else term)
+            ib.assert_within(model, ref, q, what + ', float32 between the passes', margin=1.0, term=term)
+
+
+def test_matrix_tables():
+    """One band-pass and one envelope of every section count, every envelope's families among every band-pass's, and
+    the fused forward sweep's shifted-grid pairs are those with envelopes of at most two sections."""
+    for table, names in ((ib.BANDPASSES, ib.MATRIX_BANDPASS), (ib.ENVELOPES, ib.MATRIX_ENVELOPE)):
+        assert sorted(names) == [1, 2, 3, 4]
+        assert all(len(ib.design(names[n], table)[0]) == n for n in names)
+    for (sf, se), env in ib.MATRIX_ENVELOPE_BEHIND.items():
+        assert sf in ib.MATRIX_BANDPASS and len(ib.design(env, ib.ENVELOPES)[0]) == se
+    assert len(set(ib.MATRIX_PAIRS)) == 16 and set(ib.MATRIX_PAIRS) <= set(PAIRS)
+    assert set(ib.MATRIX_SHIFTED) == {(bp, env) for bp, env in ib.MATRIX_PAIRS if len(ib.design(env, ib.ENVELOPES)[0]) <= 2}
+    for bp, env in ib.MATRIX_PAIRS:
+        assert len(ib.envelope_lanes(ib.design(bp)[2], ib.design(env, ib.ENVELOPES)[2])) >= 4
+
+
+@pytest.mark.parametrize('sections', sorted(ib.MATRIX_BANDPASS))
+def test_matrix_spectral_lanes_meet_the_cap(sections):
+    """The stationary lanes whose PSD the sweep matrix judges ride through the band-pass too, and their yf is judged like
+    every other lane's: q under the cap, the reference in range, the rounded float64 run inside the bound."""
+    bp = ib.MATRIX_BANDPASS[sections]
+    sos, rate, _ = ib.design(bp)
+    x = ib.matrix_spectral_lanes(ib.T_LONG, rate)
+    assert x.shape == (ib.T_LONG, 16)
+    ref, run = ib.sosfilt_runs(sos, x)
+    check_case(ref, run, '%s, spectral lanes' % bp)
 
 
 @pytest.mark.parametrize('case,table', [('bp2 300-3000 Hz @ 96 kHz', 'BANDPASSES'), ('bp4 300-3000 Hz @ 48 kHz', 'BANDPASSES'),
